@@ -15,12 +15,19 @@ over their stdin pipes (the start barrier) and collects one JSON line each; unde
 in a gloo (CPU) group for the same two barriers and the MAX / SUM of (seconds, tokens).  ``value`` = tokens decoded by
 all replicas / max over replicas of the wall time of the K steps.
 
-Besides the contract's fields the JSON line carries
+A plain run sets up (model, session, one prefill, graph capture), warms up, times the K steps and prints the line.  Besides
+the contract's fields that line carries
+  step_roofline the whole token against 8 TB/s (all algorithmic bytes / wall time per token) - includes launch gaps.
+``--full`` adds the measurements that take runs of their own:
+  prefill_*     a second, timed prefill of the prompt (the first one also repacks the int4 weights) and its MFMA roofline;
   roofline      for the dominant kernel: algorithmic bytes per launch / its mean duration, measured live with HIP
-                events taken from each dispatch (profiling sink of the library), against 8 TB/s;
-  step_roofline the same for the whole token (all algorithmic bytes / wall time per token) - includes launch gaps;
+                events taken from each dispatch (profiling sink of the library), against 8 TB/s; ``kernels`` per kernel;
+  sampled       generate()'s default call (temperature 0.8, top_k 200) with the sampling step inside the graph;
   cpu_baseline  the CPU oracle (a port of the reference's generate()+model) timed on this host's cores: Pythia-160M fp32
                 128 -> 64 tokens (BASELINE configs[0]) and a bounded sample of this workload's decode steps.
+``--dump-outputs DIR`` writes what the last timed step computed (DIR/logits.npy, float32: its logits row; DIR/tokens.npy,
+float64: the prompt and every decoded token up to the one that step chose) - the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -340,22 +347,38 @@ def cpu_baseline(cfg, mode, model, prompt_cpu, budget_s: float = 20.0, min_token
     return out
 
 
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """``--dump-outputs``: one ``<name>.npy`` per array (float32 / float64 numpy arrays, a few hundred KB in all)."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(d / f"{name}.npy", a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--workload", default="llama2-7b-int4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the timed prefill, per-kernel HIP events and rooflines, the sampled decode and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's logits and the decoded tokens as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline: at least 8 decode tokens of the workload (minutes on Llama-2-7B)")
+    ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline: at least 8 decode tokens of the workload (minutes on Llama-2-7B); implies --full")
     ap.add_argument("--devices", default="", help="comma list of HIP_VISIBLE_DEVICES values for the replicas spawned by --gpus N (default 0..N-1)")
     ap.add_argument("--attn-split-keys", type=int, default=0, help="A/B: window slots per sequence split of the decode attention (default: the library's)")
     ap.add_argument("--engine", type=int, default=-1, help="1 / 0: force the one-launch stream engine on / off (default: the library's choice)")
-    ap.add_argument("--no-sampled", action="store_true", help="skip the sampled-decode leg (generate's default call: temperature 0.8, top_k 200)")
+    ap.add_argument("--no-sampled", action="store_true", help="--full without the sampled-decode leg (generate's default call: temperature 0.8, top_k 200)")
     ap.add_argument("--layers", type=int, default=0, help="diagnostic: build the workload's model with this many blocks (a cache-residency probe; the line is marked and is not the metric)")
     ap.add_argument("--watchdog", type=float, default=300.0, help="seconds without a phase change before the run reports where it is stuck and exits 3 (0: off)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full or args.cpu_full
 
     rank, local, world = rank_env()
     replica = os.environ.get("PARROT_BENCH_REPLICA")
@@ -415,14 +438,16 @@ def main() -> None:
         wd.phase("first prefill (lazy W4K repacks)")
         # one untimed prefill first: the int4 weights are repacked to the kernel layout lazily at first use (a one-time
         # load cost, 161 repack launches), workspaces are allocated, code objects are loaded
-        sess.prefill(prompt.to(device))
-        torch.cuda.synchronize(device)
-        wd.phase("timed prefill")
-        t_pre = time.perf_counter()
         logits = sess.prefill(prompt.to(device))
+        if full:  # the same prompt once more, timed: prefill_ms
+            torch.cuda.synchronize(device)
+            wd.phase("timed prefill")
+            t_pre = time.perf_counter()
+            logits = sess.prefill(prompt.to(device))
         L.ops.argmax_advance(logits, sess.tokens, sess.pos)
         torch.cuda.synchronize(device)
-        t_pre = time.perf_counter() - t_pre
+        if full:
+            t_pre = time.perf_counter() - t_pre
         wd.phase("graph capture")
         sess.capture()
         wd.phase(f"warm-up, {args.warmup} steps")
@@ -437,27 +462,32 @@ def main() -> None:
         wd.phase(f"timed region, {args.steps} steps")
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            sess.step()
+            step_logits = sess.step()
         barrier(world, device)
         elapsed = time.perf_counter() - t0
         sess.check_error()  # (after the clock stopped: the check syncs)
         elapsed_max, units = max_over_ranks(elapsed, args.steps, world, device)
         pos_end = int(sess.pos.item())
         assert pos_end == T + args.warmup + args.steps, (pos_end, T, args.warmup, args.steps)
+        if args.dump_outputs and rank == 0:
+            # what the last timed step handed its caller: its logits row and the token it chose (the last of `tokens`)
+            dump_outputs(args.dump_outputs, {"logits": step_logits.float().cpu().numpy(),
+                                             "tokens": sess.tokens[: pos_end + 1].cpu().double().numpy()})
 
-        # per-kernel durations: the same step, launched eagerly with every dispatch bracketed by HIP events
-        wd.phase("per-kernel HIP events")
-        prof_steps = 8
-        _hip.prof_begin()
-        for _ in range(prof_steps):
-            sess._step()
-        stats = _hip.prof_end()
-        sess.check_error()
+        if full:
+            # per-kernel durations: the same step, launched eagerly with every dispatch bracketed by HIP events
+            wd.phase("per-kernel HIP events")
+            prof_steps = 8
+            _hip.prof_begin()
+            for _ in range(prof_steps):
+                sess._step()
+            stats = _hip.prof_end()
+            sess.check_error()
 
         # the reference's DEFAULT call samples (generate/base.py:165-166: temperature 0.8, top_k 200): the same model and
         # prompt with the sampling step inside the captured graph (torch's noise draw + parrot_topk_sample)
         sampled = None
-        if not args.no_sampled:
+        if full and not args.no_sampled:
             wd.phase("sampled decode (temperature 0.8, top_k 200)")
             n_s = min(args.steps, 128)
             s2 = _session(model, total, total, greedy=False, sampler=(0.8, 200))
@@ -482,26 +512,7 @@ def main() -> None:
     ms_per_step = elapsed_max / args.steps * 1e3
     ctx_mean = T + args.warmup + args.steps / 2.0
     w_bytes, kv_bytes = token_bytes(cfg, mode, ctx_mean)
-    kb = kernel_bytes_per_token(cfg, mode)
-    kb["eng_token"] = (w_bytes + kv_bytes, 1)  # the stream engine: the whole token is one launch
-    dom = max(stats, key=lambda k: stats[k][0])
-    kernels = {k: {"avg_us": v[0] / v[1] * 1e3, "launches_per_token": v[1] / prof_steps, "ms_per_token": v[0] / prof_steps}
-               for k, v in sorted(stats.items(), key=lambda kv: -kv[1][0])}
-    roofline = None
-    if dom in kb:
-        bytes_per_launch = kb[dom][0] / kb[dom][1]
-        avg_s = stats[dom][0] / stats[dom][1] * 1e-3
-        achieved = bytes_per_launch / avg_s / 1e9
-        run = args.workload + ("-engine" if sess.eng is not None else "-multilaunch")
-        traffic, traffic_src, traffic_problem = pmc_traffic(dom, run)
-        if traffic_problem:
-            print(f"bench.py: roofline.traffic unavailable - {traffic_problem}", file=sys.stderr, flush=True)
-        roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_problem": traffic_problem,
-                    "bytes_per_launch": bytes_per_launch,
-                    "avg_launch_us": avg_s * 1e6, "launches_per_token": kb[dom][1]}
     step_gbs = (w_bytes + kv_bytes) / (ms_per_step * 1e-3) / 1e9
-    prefill_flops = 2.0 * cfg.n_linear_params() * T - 2.0 * cfg.padded_vocab_size * cfg.n_embd * (T - 1)
 
     result = {
         "metric": "decode tokens/s (single-stream per GPU, independent replicas)",
@@ -520,37 +531,61 @@ def main() -> None:
                    + (f" - DIAGNOSTIC: {args.layers} of the model's blocks (not the metric)" if args.layers else ""),
                    "prompt_tokens": T, "replicas": world, "parallelism": f"replicas x{world} (no collective, no RCCL)",
                    "graph": "hipGraph replay per token"},
-        "roofline": roofline,
         "step_roofline": {"bound": "hbm", "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": step_gbs / HBM_PEAK_GBS, "bytes_per_token": w_bytes + kv_bytes,
                           "weight_bytes": w_bytes, "kv_bytes_mean_context": kv_bytes},
-        "kernels": kernels,
-        # the reference's own definition (generate/base.py:239-255): new tokens / wall time INCLUDING the prefill
-        "reference_definition_tokens_per_s": (args.warmup + args.steps + 1) / (t_pre + (args.warmup + args.steps) * ms_per_step * 1e-3),
-        "prefill_ms": t_pre * 1e3,
-        "prefill_tokens_per_s": T / t_pre,
-        # the prompt's Linears against the dense bf16 matrix peak (int4 / int8 weights are multiplied as bf16 / int8 MFMA operands);
-        # whole-prefill wall time, attention and norms included in the denominator, lm_head counted for the last row only
-        "prefill_roofline": {"bound": "mfma", "achieved": prefill_flops / t_pre / 1e12, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                             "frac": prefill_flops / t_pre / 1e12 / MFMA_BF16_PEAK_TFLOPS, "linear_flops": prefill_flops},
         "build_s": t_build,
         "engine": sess.eng is not None,
-        # generate()'s default call (temperature 0.8, top_k 200) with the sampling step inside the graph; greedy = `value`
-        "sampled_tokens_per_s": None if sampled is None else sampled["value"],
-        "sampled": sampled,
     }
+    if full:
+        kb = kernel_bytes_per_token(cfg, mode)
+        kb["eng_token"] = (w_bytes + kv_bytes, 1)  # the stream engine: the whole token is one launch
+        dom = max(stats, key=lambda k: stats[k][0])
+        kernels = {k: {"avg_us": v[0] / v[1] * 1e3, "launches_per_token": v[1] / prof_steps, "ms_per_token": v[0] / prof_steps}
+                   for k, v in sorted(stats.items(), key=lambda kv: -kv[1][0])}
+        roofline = None
+        if dom in kb:
+            bytes_per_launch = kb[dom][0] / kb[dom][1]
+            avg_s = stats[dom][0] / stats[dom][1] * 1e-3
+            achieved = bytes_per_launch / avg_s / 1e9
+            run = args.workload + ("-engine" if sess.eng is not None else "-multilaunch")
+            traffic, traffic_src, traffic_problem = pmc_traffic(dom, run)
+            if traffic_problem:
+                print(f"bench.py: roofline.traffic unavailable - {traffic_problem}", file=sys.stderr, flush=True)
+            roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_problem": traffic_problem,
+                        "bytes_per_launch": bytes_per_launch,
+                        "avg_launch_us": avg_s * 1e6, "launches_per_token": kb[dom][1]}
+        prefill_flops = 2.0 * cfg.n_linear_params() * T - 2.0 * cfg.padded_vocab_size * cfg.n_embd * (T - 1)
+        result.update({
+            "roofline": roofline,
+            "kernels": kernels,
+            # the reference's own definition (generate/base.py:239-255): new tokens / wall time INCLUDING the prefill
+            "reference_definition_tokens_per_s": (args.warmup + args.steps + 1) / (t_pre + (args.warmup + args.steps) * ms_per_step * 1e-3),
+            "prefill_ms": t_pre * 1e3,
+            "prefill_tokens_per_s": T / t_pre,
+            # the prompt's Linears against the dense bf16 matrix peak (int4 / int8 weights are multiplied as bf16 / int8 MFMA operands);
+            # whole-prefill wall time, attention and norms included in the denominator, lm_head counted for the last row only
+            "prefill_roofline": {"bound": "mfma", "achieved": prefill_flops / t_pre / 1e12, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                 "frac": prefill_flops / t_pre / 1e12 / MFMA_BF16_PEAK_TFLOPS, "linear_flops": prefill_flops},
+            # generate()'s default call (temperature 0.8, top_k 200) with the sampling step inside the graph; greedy = `value`
+            "sampled_tokens_per_s": None if sampled is None else sampled["value"],
+            "sampled": sampled,
+        })
     if replica is not None:  # the parent aggregates: it needs this replica's own clock
-        result.update(elapsed_s=elapsed, device=os.environ.get("HIP_VISIBLE_DEVICES", "?"), cpu_baseline=None)
-        if rank == 0 and not args.no_cpu_baseline and int(os.environ.get("PARROT_BENCH_WORLD", "1")) == 1:
-            result["cpu_baseline"] = cpu_baseline(cfg, mode, model, prompt, args.cpu_budget, 8 if args.cpu_full else 1, wd, args.workload)
+        result.update(elapsed_s=elapsed, device=os.environ.get("HIP_VISIBLE_DEVICES", "?"))
+        if full:
+            result["cpu_baseline"] = None
+            if rank == 0 and not args.no_cpu_baseline and int(os.environ.get("PARROT_BENCH_WORLD", "1")) == 1:
+                result["cpu_baseline"] = cpu_baseline(cfg, mode, model, prompt, args.cpu_budget, 8 if args.cpu_full else 1, wd, args.workload)
         wd.stop()
         print(json.dumps(result), flush=True)
         return
     if rank == 0:
-        if args.no_cpu_baseline or world > 1:
+        if full:
             result["cpu_baseline"] = None
-        else:
-            result["cpu_baseline"] = cpu_baseline(cfg, mode, model, prompt, args.cpu_budget, 8 if args.cpu_full else 1, wd, args.workload)
+            if not args.no_cpu_baseline and world == 1:
+                result["cpu_baseline"] = cpu_baseline(cfg, mode, model, prompt, args.cpu_budget, 8 if args.cpu_full else 1, wd, args.workload)
         print(json.dumps(result), flush=True)
     wd.stop()
     if world > 1:

@@ -11,7 +11,7 @@ TAG=$1; W=$2; RUN=$3; shift 3
 OUT=gpurun_out/measure_${TAG}_$RUN
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-B="bench.py --workload $W --no-cpu-baseline --no-sampled --watchdog 90 $*"
+B="bench.py --full --workload $W --no-cpu-baseline --no-sampled --watchdog 90 $*"
 echo "== $RUN: bench" | tee $OUT/progress.txt
 timeout -k 10 600 python $B --steps 256 > $OUT/${RUN}_bench.json 2> $OUT/${RUN}_bench.err || { echo "bench failed"; tail -3 $OUT/${RUN}_bench.err; exit 1; }
 echo "== $RUN: kernel stats" | tee -a $OUT/progress.txt
