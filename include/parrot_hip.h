@@ -125,6 +125,26 @@ int parrot_bf16_gemm(const void* W, const void* W2, const void* x, int ldx, int 
                      const void* residual, int ldr, void* out, int ldo, int N, int K, int epilogue,
                      const parrot_norm_t* norm, void* workspace, void* stream);
 
+/* ---- LLaMA-Adapter v2 Linear (lit_gpt/adapter_v2.py:34-53): out = epilogue(scale * (bf16(acc + bias) + adapter_bias)), rounded
+ * to bf16 after the Linear, after the adapter bias and after the scale - then the residual add / GELU / SwiGLU as above.  Host
+ * struct, device pointers inside; any pointer may be NULL (scale 1, bias 0).  scale2 / bias2 belong to the SwiGLU partner (fc_2). */
+typedef struct parrot_adapter {
+    const void* scale;  /* bf16 [N] adapter_scale */
+    const void* bias;   /* bf16 [N] adapter_bias */
+    const void* scale2; /* bf16 [N] adapter_scale of W2 (PARROT_EPI_SWIGLU only) */
+    const void* bias2;  /* bf16 [N] adapter_bias of W2 */
+} parrot_adapter_t;
+/* parrot_bf16_gemv with the affine fused into its epilogue (M <= 8: two extra bf16 loads per output column and weight, no
+ * extra launch); adapter == NULL is parrot_bf16_gemv.                                                                    */
+int parrot_bf16_gemv_adapter(const void* W, const void* W2, const void* x, int ldx, int M, const void* bias,
+                             const void* residual, int ldr, void* out, int ldo, int N, int K, int epilogue,
+                             const parrot_norm_t* norm, const parrot_adapter_t* adapter, void* stream);
+/* Prompts: the element-wise half of the adapter Linear after PARROT_EPI_NONE GEMMs.  t (t2: the SwiGLU partner's) holds
+ * bf16(acc + bias) [M][ldt]; out = epilogue(affine(t)) with the arithmetic of parrot_bf16_gemv_adapter.  out may alias
+ * residual, not t.                                                                                                       */
+int parrot_adapter_epilogue(const void* t, const void* t2, int ldt, int M, int N, const parrot_adapter_t* adapter,
+                            int epilogue, const void* residual, int ldr, void* out, int ldo, void* stream);
+
 /* ---- LLM.int8 (quantize/bnb.py:18-60; arithmetic = bitsandbytes MatMul8bitLt) ----
  * quantize the rows of a checkpoint weight as `double_quant(weight.contiguous().half())` does (quantize/bnb.py:54-60): the value
  * is first rounded to fp16 whatever its dtype - w_dtype 0: bf16, 1: fp16, 2: fp32 -, CB = rne(127*W16/absmax_row), SCB = absmax_row */
@@ -207,6 +227,19 @@ int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* 
                              const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit,
                              void* workspace, void* tickets, void* k_cache, void* v_cache, void* y,
                              int softmax_mode, void* stream);
+/* LLaMA-Adapter prefix attention (lit_gpt/adapter.py:226-254) in the same launch: ak / av [n_groups][aT][hs] bf16 (the
+ * prefix keys / values: no RoPE), gate [n_head] bf16 (gating_factor), 1 <= aT <= 64.  The workgroup that writes y attends
+ * every roped query head to all aT prefix keys (own softmax, scale 1/sqrt(hs)) and writes
+ * y = bf16(bf16(attn) + bf16(gate * bf16(prefix attn))).                                                                 */
+int parrot_attn_fused_decode_adapter(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem,
+                                     const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit,
+                                     void* workspace, void* tickets, void* k_cache, void* v_cache, void* y,
+                                     const void* ak, const void* av, const void* gate, int aT, int softmax_mode,
+                                     void* stream);
+/* The same prefix term for M rows, added in place: y[m] = bf16(y[m] + bf16(gate * bf16(prefix attn of q[m]))), after
+ * parrot_attn_decode / parrot_attn_prefill.  q: [M][n_head*hs] roped (parrot_qkv_rope_kvappend).                        */
+int parrot_attn_adapter_prefix(const void* q, int M, const void* ak, const void* av, const void* gate, int aT, int n_groups,
+                               int q_per_kv, int hs, void* y, int ldy, int softmax_mode, void* stream);
 /* ---- small ops of the step ----------------------------------------------------------
  * x[m] = wte[tokens[(pos ? *pos : 0) + m]]   (lit_gpt/model.py:99)                    */
 int parrot_embedding(const void* wte, int d, const int64_t* tokens, const int32_t* pos, int M,

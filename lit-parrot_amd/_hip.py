@@ -30,6 +30,15 @@ class ParrotNorm(C.Structure):
 
 _np = C.POINTER(ParrotNorm)
 
+
+class ParrotAdapter(C.Structure):
+    """``parrot_adapter_t`` of include/parrot_hip.h: the adapter-v2 vectors of a Linear (and of its SwiGLU partner)."""
+
+    _fields_ = [("scale", C.c_void_p), ("bias", C.c_void_p), ("scale2", C.c_void_p), ("bias2", C.c_void_p)]
+
+
+_ap = C.POINTER(ParrotAdapter)
+
 # ---- stream engine (parrot_eng_op_t / parrot_eng_state_t of include/parrot_hip.h)
 ENG_GEMV, ENG_ATTN = 0, 1
 ENG_EPI_LOGITS = 4
@@ -75,6 +84,8 @@ SIGNATURES = {
     "parrot_w4_gemm": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _np, _vp, _vp]),
     "parrot_bf16_gemv": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _np, _vp]),
     "parrot_bf16_gemm": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _np, _vp, _vp]),
+    "parrot_bf16_gemv_adapter": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _np, _ap, _vp]),
+    "parrot_adapter_epilogue": (_i, [_vp, _vp, _i, _i, _i, _ap, _i, _vp, _i, _vp, _i, _vp]),
     "parrot_w8_quantize_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "parrot_w8_prep_act": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _np, _vp]),
     "parrot_w8_gemv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
@@ -87,6 +98,8 @@ SIGNATURES = {
     "parrot_attn_workspace_floats": (_i64, [_i, _i, _i, _i]),
     "parrot_attn_decode": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_fused_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "parrot_attn_fused_decode_adapter": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "parrot_attn_adapter_prefix": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "parrot_attn_prefill_scratch_elems": (_i64, [_i, _i, _i]),
     "parrot_attn_prefill": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "parrot_e4_bytes": (_i64, [_i, _i, _i]),

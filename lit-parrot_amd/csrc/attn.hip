@@ -385,13 +385,131 @@ static unsigned long long* g_attn_dbg_host = nullptr;  // diagnostic build only:
 static constexpr unsigned long long* g_attn_dbg_host = nullptr;
 #endif
 
-template <int HS, int HQ, int WAVES, bool PM = false>  // PM: "softmax_mode 1", see attn_decode_kernel
+// ------------------------------------------------------------------------------------------ LLaMA-Adapter prefix
+// lit_gpt/adapter.py:226-254: every roped query row attends to ALL aT prefix keys of its group (no mask, no RoPE on the prefix,
+// a softmax of its own, scale 1/sqrt(hs)) and y = y + gating_factor * ay, each of the three results rounded to bf16.
+// One wave per (row, head): lane j scores prefix key j, then each lane owns the output dims lane, lane + 64.  Both kernels that
+// add the term (the fused decode step and the multi-row pass) call this one function, so they agree bit for bit.
+constexpr int kAdapterMaxT = 64;
+
+struct AdapterAttnArgs {
+    const bf16_t* ak;    // [n_groups][aT][HS]
+    const bf16_t* av;    // [n_groups][aT][HS]
+    const bf16_t* gate;  // [n_head]
+    int aT;
+};
+
+template <int HS>
+__device__ __forceinline__ void adapter_prefix_wave(const bf16_t* q, const bf16_t* __restrict__ ak, const bf16_t* __restrict__ av,
+                                                    int aT, bool pm, float (&ay)[(HS + 63) / 64]) {
+    constexpr int ND = (HS + 63) / 64, PV = 8;  // output dims per lane; prefix value rows requested per batch
+    const int lane = threadIdx.x & 63;
+    const float scale = 1.0f / sqrtf((float)HS);
+    // the first PV value rows do not depend on the scores: requested here, their latency hides behind the score loop (rows past aT
+    // are clamped and never used)
+    float vb[ND][PV];
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+#pragma unroll
+        for (int u = 0; u < PV; ++u) vb[i][u] = bf2f(av[(int64_t)min(u, aT - 1) * HS + min(lane + 64 * i, HS - 1)]);
+    float s = -INFINITY;
+    if (lane < aT) {
+        const uint4* kr = reinterpret_cast<const uint4*>(ak + (int64_t)lane * HS);
+        const uint4* qr = reinterpret_cast<const uint4*>(q);
+        float p0 = 0.f, p1 = 0.f;
+#pragma unroll 4  // (fully unrolled, the 2 x HS/8 16-B loads of a 128-dim row are all hoisted: the 16-wave kernel spilled)
+        for (int c = 0; c < HS / 8; ++c) {
+            const uint4 kv = kr[c], qv = qr[c];
+            p0 = dot2_bf16(kv.x, qv.x, p0);
+            p1 = dot2_bf16(kv.y, qv.y, p1);
+            p0 = dot2_bf16(kv.z, qv.z, p0);
+            p1 = dot2_bf16(kv.w, qv.w, p1);
+        }
+        s = __fmul_rn(__fadd_rn(p0, p1), scale);
+    }
+    const float mx = wave_max(s);
+    const float p = lane < aT ? expf(__fsub_rn(s, mx)) : 0.f;
+    const float l = wave_sum(p);
+    const float pr = pm ? rbf(p) : p;  // softmax_mode 1: the probabilities rounded to bf16 before P.V, the sum from the unrounded ones
+    // P.V in key order (a = fma(p_j, v_j, a), j = 0 .. aT-1), PV value rows per batch requested together
+    float acc[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) acc[i] = 0.f;
+    for (int j0 = 0; j0 < aT; j0 += PV) {
+        if (j0 > 0) {
+#pragma unroll
+            for (int i = 0; i < ND; ++i)
+#pragma unroll
+                for (int u = 0; u < PV; ++u)
+                    vb[i][u] = bf2f(av[(int64_t)min(j0 + u, aT - 1) * HS + min(lane + 64 * i, HS - 1)]);
+        }
+#pragma unroll
+        for (int u = 0; u < PV; ++u) {
+            if (j0 + u < aT) {  // wave-uniform
+                const float pj = __shfl(pr, j0 + u, 64);
+#pragma unroll
+                for (int i = 0; i < ND; ++i) acc[i] = fmaf(pj, vb[i][u], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < ND; ++i) ay[i] = rbf(__fdiv_rn(acc[i], l));
+}
+
+// y = bf16(y + bf16(gate * ay)) (the gating product and the sum rounded separately, as two bf16 tensor ops do)
+__device__ __forceinline__ bf16_t adapter_combine(float y, float gate, float ay) {
+    return f2bf(__fadd_rn(y, rbf(__fmul_rn(gate, ay))));
+}
+
+// LDS of the fused kernel's prefix outputs; only the AD instantiations call this, so the plain kernel allocates nothing
+template <int N>
+__device__ __forceinline__ float* adapter_lds() {
+    __shared__ float buf[N];
+    return buf;
+}
+
+// the fused kernel's workgroup: wave hh < HQ computes query head h0 + hh of group g into sh_ay[hh][*]
+template <int HS, int HQ, bool PM>
+__device__ __forceinline__ void adapter_prefix_heads(const AdapterAttnArgs& aa, const bf16_t (*sh_q)[HS], int g, int h0, int q_per_kv,
+                                                     float* sh_ay) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave < HQ && h0 + wave < q_per_kv) {
+        float ay[(HS + 63) / 64];
+        adapter_prefix_wave<HS>(sh_q[h0 + wave], aa.ak + (int64_t)g * aa.aT * HS, aa.av + (int64_t)g * aa.aT * HS, aa.aT, PM, ay);
+#pragma unroll
+        for (int i = 0; i < (HS + 63) / 64; ++i)
+            if (lane + 64 * i < HS) sh_ay[wave * HS + lane + 64 * i] = ay[i];
+    }
+}
+
+// multi-row pass (prompts, rope_local, the unfused single-row path): one wave per (head, row), in place on y
+template <int HS>
+__global__ void __launch_bounds__(64)
+attn_adapter_prefix_kernel(const bf16_t* __restrict__ q, int n_head, AdapterAttnArgs aa, int q_per_kv, bf16_t* y, int ldy, int pm) {
+    const int head = blockIdx.x, m = blockIdx.y, lane = threadIdx.x;
+    const int g = head / q_per_kv;
+    float ay[(HS + 63) / 64];
+    adapter_prefix_wave<HS>(q + ((int64_t)m * n_head + head) * HS, aa.ak + (int64_t)g * aa.aT * HS, aa.av + (int64_t)g * aa.aT * HS,
+                            aa.aT, pm != 0, ay);
+    const float gate = bf2f(aa.gate[head]);
+#pragma unroll
+    for (int i = 0; i < (HS + 63) / 64; ++i) {
+        const int d = lane + 64 * i;
+        if (d < HS) {
+            bf16_t* yp = y + (int64_t)m * ldy + (int64_t)head * HS + d;
+            *yp = adapter_combine(bf2f(*yp), gate, ay[i]);
+        }
+    }
+}
+
+// AD: the LLaMA-Adapter prefix term is added by the workgroup that writes y (AD = false is the plain kernel)
+template <int HS, int HQ, int WAVES, bool PM = false, bool AD = false>  // PM: "softmax_mode 1", see attn_decode_kernel
 __global__ void __launch_bounds__(WAVES * 64)
 attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restrict__ rope_cos,
                          const __half* __restrict__ rope_sin, int n_elem, const int32_t* __restrict__ pos_ptr,
                          bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache, int n_groups, int q_per_kv, int S,
                          int nsplit, float* __restrict__ ws, unsigned int* __restrict__ tickets, bf16_t* __restrict__ y,
-                         unsigned long long* dbg) {
+                         unsigned long long* dbg, AdapterAttnArgs aa) {
     constexpr int LPR = HS / 8;
     constexpr int RPW = 64 / LPR;
     attn_stamp(dbg, 0);
@@ -589,6 +707,9 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
                 }
             }
         }
+        if constexpr (AD) {
+            if (nsplit == 1) adapter_prefix_heads<HS, HQ, PM>(aa, sh_q, g, h0, q_per_kv, adapter_lds<HQ * HS>());
+        }
         __syncthreads();
         attn_stamp(dbg, 3);
         for (int idx = threadIdx.x; idx < HQ * HS; idx += WAVES * 64) {
@@ -606,7 +727,10 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
                 }
                 const int head = g * q_per_kv + h0 + hh;
                 if (nsplit == 1) {
-                    y[(int64_t)head * HS + d] = f2bf(a / l);
+                    if constexpr (AD)
+                        y[(int64_t)head * HS + d] = adapter_combine(rbf(a / l), bf2f(aa.gate[head]), adapter_lds<HQ * HS>()[hh * HS + d]);
+                    else
+                        y[(int64_t)head * HS + d] = f2bf(a / l);
                 } else {
                     float* p = ws + ((int64_t)head * nsplit + split) * (HS + 2);
                     store_agent(p + d, a);
@@ -630,6 +754,10 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     }
     __syncthreads();
     if (!sh_last) return;
+    if constexpr (AD) {
+        adapter_prefix_heads<HS, HQ, PM>(aa, sh_q, g, h0, q_per_kv, adapter_lds<HQ * HS>());
+        __syncthreads();
+    }
     for (int idx = threadIdx.x; idx < HQ * HS; idx += WAVES * 64) {
         const int hq = h0 + idx / HS, d = idx % HS;
         if (hq >= q_per_kv) continue;
@@ -644,14 +772,17 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
             l += load_agent(p + t * (HS + 2) + HS + 1) * wgt;
             a += load_agent(p + t * (HS + 2) + d) * wgt;
         }
-        y[(int64_t)head * HS + d] = f2bf(a / l);
+        if constexpr (AD)
+            y[(int64_t)head * HS + d] = adapter_combine(rbf(a / l), bf2f(aa.gate[head]), adapter_lds<HQ * HS>()[(idx / HS) * HS + d]);
+        else
+            y[(int64_t)head * HS + d] = f2bf(a / l);
     }
 }
 
-template <int HS>
+template <int HS, bool AD = false>
 static int attn_fused_launch(const void* qkv, const void* cosp, const void* sinp, int n_elem, const int32_t* pos,
                              void* k_cache, void* v_cache, int n_groups, int q_per_kv, int S, int nsplit, void* ws,
-                             void* tickets, void* y, int softmax_mode, hipStream_t st) {
+                             void* tickets, void* y, int softmax_mode, hipStream_t st, AdapterAttnArgs aa = {}) {
     const int hq = q_per_kv == 1 ? 1 : (q_per_kv == 2 ? 2 : 4);
     // 16 waves when a split holds more keys than 4 waves cover in two steps
     const int per = (S + nsplit - 1) / nsplit;
@@ -660,12 +791,12 @@ static int attn_fused_launch(const void* qkv, const void* cosp, const void* sinp
 #define PARROT_FUSED_GO(HQV, WV)                                                                                            \
     do {                                                                                                                    \
         if (softmax_mode == 1)                                                                                              \
-            return launch(K_ATTN_FUSED, attn_fused_decode_kernel<HS, HQV, 16, true>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
+            return launch(K_ATTN_FUSED, attn_fused_decode_kernel<HS, HQV, 16, true, AD>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
                           (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups, \
-                          q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host);             \
-        return launch(K_ATTN_FUSED, attn_fused_decode_kernel<HS, HQV, WV>, grid, block, 0, st, (const bf16_t*)qkv,          \
+                          q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa);         \
+        return launch(K_ATTN_FUSED, attn_fused_decode_kernel<HS, HQV, WV, false, AD>, grid, block, 0, st, (const bf16_t*)qkv, \
                       (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups,   \
-                      q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host);                 \
+                      q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa);             \
     } while (0)
     if (wide) {
         if (q_per_kv == 1) PARROT_FUSED_GO(1, 16);
@@ -747,9 +878,9 @@ static int check_softmax_mode(const char* who, int softmax_mode, int S, int nspl
     return PARROT_OK;
 }
 
-int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
-                             int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
-                             void* k_cache, void* v_cache, void* y, int softmax_mode, void* stream) {
+static int attn_fused_entry(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
+                            int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
+                            void* k_cache, void* v_cache, void* y, int softmax_mode, const AdapterAttnArgs* aa, void* stream) {
     {
         const int rc = check_softmax_mode("attn_fused_decode", softmax_mode, S, nsplit);
         if (rc != PARROT_OK) return rc;
@@ -763,14 +894,72 @@ int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* 
     PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "attn_fused_decode: workspace and tickets required when nsplit > 1");
     PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "attn_fused_decode: 16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
+#define PARROT_FUSED_HS(HSV)                                                                                                      \
+    case HSV:                                                                                                                     \
+        if (aa)                                                                                                                   \
+            return attn_fused_launch<HSV, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, \
+                                                workspace, tickets, y, softmax_mode, st, *aa);                                     \
+        return attn_fused_launch<HSV>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, \
+                                      tickets, y, softmax_mode, st);
     switch (hs) {
-        case 32: return attn_fused_launch<32>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, tickets, y, softmax_mode, st);
-        case 64: return attn_fused_launch<64>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, tickets, y, softmax_mode, st);
-        case 128: return attn_fused_launch<128>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, tickets, y, softmax_mode, st);
+        PARROT_FUSED_HS(32)
+        PARROT_FUSED_HS(64)
+        PARROT_FUSED_HS(128)
         default: break;
     }
+#undef PARROT_FUSED_HS
     set_error("attn_fused_decode: head size %d not built (32, 64, 128)", hs);
     return PARROT_EUNSUPPORTED;
+}
+
+int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
+                             int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
+                             void* k_cache, void* v_cache, void* y, int softmax_mode, void* stream) {
+    return attn_fused_entry(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache,
+                            v_cache, y, softmax_mode, nullptr, stream);
+}
+
+// prefix K/V, gate and aT of the two adapter entry points
+static int check_adapter_attn(const char* who, const void* ak, const void* av, const void* gate, int aT, int n_groups, int q_per_kv,
+                              int hs, AdapterAttnArgs* aa) {
+    PARROT_REQUIRE(ak && av && gate, "%s: null adapter pointer", who);
+    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && aT >= 1, "%s: bad shape n_groups=%d q_per_kv=%d aT=%d", who, n_groups, q_per_kv, aT);
+    PARROT_UNSUPPORTED(aT <= kAdapterMaxT, "%s: adapter_prompt_length %d > %d is not built (one prefix key per lane)", who, aT, kAdapterMaxT);
+    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
+    PARROT_REQUIRE(aligned16(ak) && aligned16(av) && (reinterpret_cast<uintptr_t>(gate) & 1u) == 0, "%s: ak / av must be 16-byte aligned", who);
+    *aa = AdapterAttnArgs{(const bf16_t*)ak, (const bf16_t*)av, (const bf16_t*)gate, aT};
+    return PARROT_OK;
+}
+
+int parrot_attn_fused_decode_adapter(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
+                                     int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
+                                     void* k_cache, void* v_cache, void* y, const void* ak, const void* av, const void* gate, int aT,
+                                     int softmax_mode, void* stream) {
+    AdapterAttnArgs aa;
+    const int rc = check_adapter_attn("attn_fused_decode_adapter", ak, av, gate, aT, n_groups, q_per_kv, hs, &aa);
+    if (rc != PARROT_OK) return rc;
+    return attn_fused_entry(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache,
+                            v_cache, y, softmax_mode, &aa, stream);
+}
+
+int parrot_attn_adapter_prefix(const void* q, int M, const void* ak, const void* av, const void* gate, int aT, int n_groups,
+                               int q_per_kv, int hs, void* y, int ldy, int softmax_mode, void* stream) {
+    AdapterAttnArgs aa;
+    int rc = check_adapter_attn("attn_adapter_prefix", ak, av, gate, aT, n_groups, q_per_kv, hs, &aa);
+    if (rc != PARROT_OK) return rc;
+    PARROT_REQUIRE(q && y, "attn_adapter_prefix: null pointer");
+    PARROT_REQUIRE(softmax_mode == 0 || softmax_mode == 1, "attn_adapter_prefix: softmax_mode must be 0 or 1");
+    PARROT_REQUIRE(M >= 1 && M <= 65535 && n_groups * q_per_kv <= 65535, "attn_adapter_prefix: M / n_head out of range");
+    PARROT_REQUIRE(ldy >= n_groups * q_per_kv * hs, "attn_adapter_prefix: ldy too small");
+    PARROT_REQUIRE(aligned16(q), "attn_adapter_prefix: q must be 16-byte aligned");
+    const int n_head = n_groups * q_per_kv;
+    const dim3 grid(n_head, M);
+    hipStream_t st = (hipStream_t)stream;
+    switch (hs) {
+        case 32: return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<32>, grid, dim3(64), 0, st, (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
+        case 64: return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<64>, grid, dim3(64), 0, st, (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
+        default: return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<128>, grid, dim3(64), 0, st, (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
+    }
 }
 
 int64_t parrot_attn_workspace_floats(int M, int n_head, int hs, int nsplit) {

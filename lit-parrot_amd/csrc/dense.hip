@@ -18,11 +18,12 @@ namespace parrot {
 constexpr int kDenseJ = 4;         // 16-B loads per lane per row (max)
 constexpr int kDenseMaxSlabs = 16;  // K <= 32768
 
-template <int M, bool DUAL, int J, int RU, int MAXW>
+// AD: the adapter-v2 affine in the epilogue (its four elements requested at batch start like the bias); AD = false is the plain kernel
+template <int M, bool DUAL, int J, int RU, int MAXW, bool AD = false>
 __global__ void __launch_bounds__(MAXW * 64)
 bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const bf16_t* __restrict__ x, int ldx,
                  const bf16_t* __restrict__ bias, const bf16_t* residual, int ldr, bf16_t* out, int ldo, int N, int K,
-                 int wps, int nslabs, int epi, int iters, NormArgs na) {
+                 int wps, int nslabs, int epi, int iters, NormArgs na, AdapterArgs ad) {
     constexpr int NW = DUAL ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char dense_smem[];  // normalised activations [M][K] bf16 (norm only)
     __shared__ float red[2][MAXW][RU * M * NW];
@@ -161,6 +162,13 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
         const int e_col = min(((int)blockIdx.x + t * (int)gridDim.x) * R + e_ur, N - 1);
         const bf16_t e_res = res_p[residual != nullptr ? (int64_t)e_m * ldr + e_col : 0];
         const bf16_t e_bias = bias_p[bias != nullptr ? e_col : 0];
+        float e_as = 1.f, e_ab = 0.f, e_as2 = 1.f, e_ab2 = 0.f;
+        if constexpr (AD) {
+            if (ad.scale != nullptr) e_as = bf2f(ad.scale[e_col]);
+            if (ad.bias != nullptr) e_ab = bf2f(ad.bias[e_col]);
+            if (DUAL && ad.scale2 != nullptr) e_as2 = bf2f(ad.scale2[e_col]);
+            if (DUAL && ad.bias2 != nullptr) e_ab2 = bf2f(ad.bias2[e_col]);
+        }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             if (u + PRIME < RU) {
@@ -207,7 +215,11 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
                     a0 += rd[c * wps + jj][(u * M + m) * NW];
                     if (DUAL) a1 += rd[c * wps + jj][(u * M + m) * NW + 1];
                 }
-                out[(int64_t)m * ldo + col] = apply_epilogue_vals(epi, a0, a1, bias != nullptr, bf2f(e_bias), bf2f(e_res));
+                if constexpr (AD)
+                    out[(int64_t)m * ldo + col] = apply_epilogue_adapter_vals(epi, a0, a1, bias != nullptr, bf2f(e_bias), bf2f(e_res),
+                                                                              e_as, e_ab, e_as2, e_ab2);
+                else
+                    out[(int64_t)m * ldo + col] = apply_epilogue_vals(epi, a0, a1, bias != nullptr, bf2f(e_bias), bf2f(e_res));
             }
         }
     }
@@ -218,7 +230,7 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
 template <int M, int J, int MAXW>
 static int bf16_gemv_launch_jw(const void* W, const void* W2, const void* x, int ldx, const void* bias,
                                const void* residual, int ldr, void* out, int ldo, int N, int K, int epi, const NormArgs& na,
-                               int nslabs, hipStream_t st) {
+                               int nslabs, const AdapterArgs* ad, hipStream_t st) {
     constexpr int RU = 4, RUD = 2;  // rows per wave and batch (single weight / SwiGLU pair)
     const bool dual = epi == PARROT_EPI_SWIGLU;
     const int ru = dual ? RUD : RU;
@@ -240,21 +252,26 @@ static int bf16_gemv_launch_jw(const void* W, const void* W2, const void* x, int
     const int resident = 256 * (4 * per_simd / (nslabs * wps) > 0 ? 4 * per_simd / (nslabs * wps) : 1);
     const int iters = (batches + resident - 1) / resident;
     const dim3 grid((batches + iters - 1) / iters), block(nthreads);
-    if (dual)
-        return launch(K_BF16_GEMV_DUAL, bf16_gemv_kernel<M, true, J, RUD, MAXW>, grid, block, lds, st, (const uint4*)W,
-                      (const uint4*)W2, (const bf16_t*)x, ldx, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                      (bf16_t*)out, ldo, N, K, wps, nslabs, epi, iters, na);
-    return launch(K_BF16_GEMV, bf16_gemv_kernel<M, false, J, RU, MAXW>, grid, block, lds, st, (const uint4*)W,
-                  (const uint4*)W2, (const bf16_t*)x, ldx, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out,
-                  ldo, N, K, wps, nslabs, epi, iters, na);
+    const AdapterArgs adv = ad ? *ad : AdapterArgs{nullptr, nullptr, nullptr, nullptr};
+#define PARROT_DENSE_GO(KID, DUALV, RUV, ADV)                                                                             \
+    return launch(KID, bf16_gemv_kernel<M, DUALV, J, RUV, MAXW, ADV>, grid, block, lds, st, (const uint4*)W, (const uint4*)W2, \
+                  (const bf16_t*)x, ldx, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, N, K, wps,      \
+                  nslabs, epi, iters, na, adv)
+    if (dual) {
+        if (ad) PARROT_DENSE_GO(K_BF16_GEMV_DUAL, true, RUD, true);
+        PARROT_DENSE_GO(K_BF16_GEMV_DUAL, true, RUD, false);
+    }
+    if (ad) PARROT_DENSE_GO(K_BF16_GEMV, false, RU, true);
+    PARROT_DENSE_GO(K_BF16_GEMV, false, RU, false);
+#undef PARROT_DENSE_GO
 }
 
 template <int M, int J>
 static int bf16_gemv_launch_j(const void* W, const void* W2, const void* x, int ldx, const void* bias,
                               const void* residual, int ldr, void* out, int ldo, int N, int K, int epi, const NormArgs& na,
-                              int nslabs, hipStream_t st) {
-    if (nslabs <= 8) return bf16_gemv_launch_jw<M, J, 8>(W, W2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, nslabs, st);
-    if constexpr (J <= 4) return bf16_gemv_launch_jw<M, J, 16>(W, W2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, nslabs, st);
+                              int nslabs, const AdapterArgs* ad, hipStream_t st) {
+    if (nslabs <= 8) return bf16_gemv_launch_jw<M, J, 8>(W, W2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, nslabs, ad, st);
+    if constexpr (J <= 4) return bf16_gemv_launch_jw<M, J, 16>(W, W2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, nslabs, ad, st);
     set_error("bf16_gemv: K=%d needs more than 8 slabs of %d loads", K, J);
     return PARROT_EUNSUPPORTED;
 }
@@ -262,13 +279,13 @@ static int bf16_gemv_launch_j(const void* W, const void* W2, const void* x, int 
 template <int M>
 static int bf16_gemv_launch(const void* W, const void* W2, const void* x, int ldx, const void* bias,
                             const void* residual, int ldr, void* out, int ldo, int N, int K, int epi, const NormArgs& na,
-                            hipStream_t st) {
+                            const AdapterArgs* ad, hipStream_t st) {
     const int chunks = K / 8;
     const int nslabs = (chunks + 64 * kDenseJ - 1) / (64 * kDenseJ);
     const int per_slab = (chunks + nslabs - 1) / nslabs;  // 16-B units of the largest slab
     const int jn = (per_slab + 63) / 64;
 #define PARROT_DENSE_J(JV) \
-    if (jn <= JV) return bf16_gemv_launch_j<M, JV>(W, W2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, nslabs, st)
+    if (jn <= JV) return bf16_gemv_launch_j<M, JV>(W, W2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, nslabs, ad, st)
     PARROT_DENSE_J(1);
     PARROT_DENSE_J(2);
     PARROT_DENSE_J(3);
@@ -282,11 +299,11 @@ static int bf16_gemv_launch(const void* W, const void* W2, const void* x, int ld
 
 using namespace parrot;
 
-extern "C" {
+namespace parrot {
 
-int parrot_bf16_gemv(const void* W, const void* W2, const void* x, int ldx, int M, const void* bias,
-                     const void* residual, int ldr, void* out, int ldo, int N, int K, int epilogue,
-                     const parrot_norm_t* norm, void* stream) {
+static int bf16_gemv_entry(const void* W, const void* W2, const void* x, int ldx, int M, const void* bias, const void* residual,
+                           int ldr, void* out, int ldo, int N, int K, int epilogue, const parrot_norm_t* norm,
+                           const AdapterArgs* ad, void* stream) {
     int rc = check_linear_args("bf16_gemv", W, W2, x, ldx, M, residual, ldr, out, ldo, N, K, epilogue);
     if (rc != PARROT_OK) return rc;
     PARROT_UNSUPPORTED(K % 8 == 0, "bf16_gemv: K=%d must be a multiple of 8", K);
@@ -304,12 +321,77 @@ int parrot_bf16_gemv(const void* W, const void* W2, const void* x, int ldx, int 
         const void* rm = rb ? rb + (int64_t)m0 * ldr : nullptr;
         void* om = ob + (int64_t)m0 * ldo;
         if (M - m0 >= 2)
-            rc = bf16_gemv_launch<2>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, st);
+            rc = bf16_gemv_launch<2>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, ad, st);
         else
-            rc = bf16_gemv_launch<1>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, st);
+            rc = bf16_gemv_launch<1>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, ad, st);
         if (rc != PARROT_OK) return rc;
     }
     return PARROT_OK;
+}
+
+// adapter-v2 vectors of the GEMV / element-wise entry points: every vector given is 2-byte aligned device memory; the partner's
+// pair only with a partner
+int make_adapter_args(const char* who, const parrot_adapter_t* adapter, int epilogue, AdapterArgs* ad) {
+    *ad = AdapterArgs{nullptr, nullptr, nullptr, nullptr};
+    if (adapter == nullptr) return PARROT_OK;
+    PARROT_REQUIRE(epilogue == PARROT_EPI_SWIGLU || (adapter->scale2 == nullptr && adapter->bias2 == nullptr),
+                   "%s: scale2 / bias2 belong to the SWIGLU partner", who);
+    for (const void* p : {adapter->scale, adapter->bias, adapter->scale2, adapter->bias2})
+        PARROT_REQUIRE((reinterpret_cast<uintptr_t>(p) & 1u) == 0, "%s: misaligned adapter vector", who);
+    ad->scale = (const bf16_t*)adapter->scale;
+    ad->bias = (const bf16_t*)adapter->bias;
+    ad->scale2 = (const bf16_t*)adapter->scale2;
+    ad->bias2 = (const bf16_t*)adapter->bias2;
+    return PARROT_OK;
+}
+
+// one thread per output element: out = epilogue(affine(t)), t = bf16(acc + bias) of a PARROT_EPI_NONE GEMM (prompts)
+__global__ void __launch_bounds__(256)
+adapter_epilogue_kernel(const bf16_t* __restrict__ t, const bf16_t* __restrict__ t2, int ldt, int M, int N, AdapterArgs ad, int epi,
+                        const bf16_t* residual, int ldr, bf16_t* out, int ldo) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
+    if (col >= N || m >= M) return;
+    const float v = bf2f(t[(int64_t)m * ldt + col]);
+    const float v2 = epi == PARROT_EPI_SWIGLU ? bf2f(t2[(int64_t)m * ldt + col]) : 0.f;
+    const float res = epi == PARROT_EPI_RESIDUAL ? bf2f(residual[(int64_t)m * ldr + col]) : 0.f;
+    const float a_s = ad.scale ? bf2f(ad.scale[col]) : 1.f, a_b = ad.bias ? bf2f(ad.bias[col]) : 0.f;
+    const float a_s2 = ad.scale2 ? bf2f(ad.scale2[col]) : 1.f, a_b2 = ad.bias2 ? bf2f(ad.bias2[col]) : 0.f;
+    out[(int64_t)m * ldo + col] = apply_epilogue_adapter_vals(epi, v, v2, false, 0.f, res, a_s, a_b, a_s2, a_b2);
+}
+
+}  // namespace parrot
+
+extern "C" {
+
+int parrot_bf16_gemv(const void* W, const void* W2, const void* x, int ldx, int M, const void* bias,
+                     const void* residual, int ldr, void* out, int ldo, int N, int K, int epilogue,
+                     const parrot_norm_t* norm, void* stream) {
+    return bf16_gemv_entry(W, W2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, norm, nullptr, stream);
+}
+
+int parrot_bf16_gemv_adapter(const void* W, const void* W2, const void* x, int ldx, int M, const void* bias,
+                             const void* residual, int ldr, void* out, int ldo, int N, int K, int epilogue,
+                             const parrot_norm_t* norm, const parrot_adapter_t* adapter, void* stream) {
+    AdapterArgs ad;
+    const int rc = make_adapter_args("bf16_gemv_adapter", adapter, epilogue, &ad);
+    if (rc != PARROT_OK) return rc;
+    return bf16_gemv_entry(W, W2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, norm, adapter ? &ad : nullptr, stream);
+}
+
+int parrot_adapter_epilogue(const void* t, const void* t2, int ldt, int M, int N, const parrot_adapter_t* adapter, int epilogue,
+                            const void* residual, int ldr, void* out, int ldo, void* stream) {
+    PARROT_REQUIRE(t && out, "adapter_epilogue: null pointer");
+    PARROT_REQUIRE(M >= 1 && N >= 1 && M <= 65535, "adapter_epilogue: bad shape M=%d N=%d", M, N);
+    PARROT_REQUIRE(epilogue >= PARROT_EPI_NONE && epilogue <= PARROT_EPI_SWIGLU, "adapter_epilogue: unknown epilogue %d", epilogue);
+    PARROT_REQUIRE((epilogue == PARROT_EPI_SWIGLU) == (t2 != nullptr), "adapter_epilogue: second input iff SWIGLU");
+    PARROT_REQUIRE((epilogue == PARROT_EPI_RESIDUAL) == (residual != nullptr), "adapter_epilogue: residual iff RESIDUAL epilogue");
+    PARROT_REQUIRE(ldt >= N && ldo >= N && (!residual || ldr >= N), "adapter_epilogue: leading dimension too small");
+    PARROT_REQUIRE(out != t && (!t2 || out != t2), "adapter_epilogue: out must not alias the GEMM result");
+    AdapterArgs ad;
+    const int rc = make_adapter_args("adapter_epilogue", adapter, epilogue, &ad);
+    if (rc != PARROT_OK) return rc;
+    return launch(K_ADAPTER_EPI, adapter_epilogue_kernel, dim3((N + 255) / 256, M), dim3(256), 0, (hipStream_t)stream,
+                  (const bf16_t*)t, (const bf16_t*)t2, ldt, M, N, ad, epilogue, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo);
 }
 
 }  // extern "C"

@@ -93,6 +93,8 @@ enum KernelId : int {
     K_W8_DEQUANT,
     K_W8_OUTLIER,
     K_TOPK_SAMPLE,
+    K_ADAPTER_EPI,
+    K_ATTN_ADAPTER_PREFIX,
     K_COUNT
 };
 
@@ -317,6 +319,30 @@ __device__ __forceinline__ bf16_t apply_epilogue_vals(int epi, float acc, float 
         v = gelu_erf(v);
     } else if (epi == PARROT_EPI_SWIGLU) {
         v = rbf(silu(v)) * rbf(acc2);
+    }
+    return f2bf(v);
+}
+// adapter-v2 Linear (lit_gpt/adapter_v2.py:34-53): adapter_scale * (F.linear(x, W, b) + adapter_bias) in bf16 is three roundings
+// - bf16(acc + b), + adapter_bias, * adapter_scale - and only then the residual add / GELU / SwiGLU (whose partner fc_2 carries its
+// own pair).  Vectors the model does not have enter as scale 1 / bias 0.
+struct AdapterArgs {
+    const bf16_t* scale;
+    const bf16_t* bias;
+    const bf16_t* scale2;  // SwiGLU partner
+    const bf16_t* bias2;
+};
+__device__ __forceinline__ float adapter_affine(float v, float a_s, float a_b) { return rbf(rbf(v + a_b) * a_s); }
+__device__ __forceinline__ bf16_t apply_epilogue_adapter_vals(int epi, float acc, float acc2, bool has_bias, float bias_v, float res,
+                                                              float a_s, float a_b, float a_s2, float a_b2) {
+    float v = acc;
+    if (has_bias) v += bias_v;
+    v = adapter_affine(rbf(v), a_s, a_b);
+    if (epi == PARROT_EPI_RESIDUAL) {
+        v = res + v;
+    } else if (epi == PARROT_EPI_GELU) {
+        v = gelu_erf(v);
+    } else if (epi == PARROT_EPI_SWIGLU) {
+        v = rbf(silu(v)) * adapter_affine(rbf(acc2), a_s2, a_b2);
     }
     return f2bf(v);
 }

@@ -120,6 +120,8 @@ class StreamEngine:
     def supported(model) -> Optional[str]:
         """None if the model can run on the engine, else the reason."""
         c = model.config
+        if any(hasattr(m, n) for m in model.modules() for n in ("adapter_wte", "gating_factor", "adapter_scale", "adapter_bias")):
+            return "adapter prefix / adapter-v2 Linears (the engine's step has neither)"
         linears = [m for m in model.modules() if isinstance(m, torch.nn.Linear) or hasattr(m, "hip_linear")]
         if not linears:
             return "no Linear layers"

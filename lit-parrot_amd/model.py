@@ -102,15 +102,32 @@ def _linear(mod: nn.Module, x: torch.Tensor, out: torch.Tensor, *, epilogue: int
             if m is not None and id(m) in LINEAR_OBSERVERS:
                 LINEAR_OBSERVERS[id(m)](x)
     norm = _fused_norm(norm)
+    adapter = _adapter_v2(mod, partner)
     if hasattr(mod, "hip_linear"):
+        if adapter is not None:
+            raise ParrotHipError(f"{type(mod).__name__} carries adapter-v2 parameters (adapter_scale / adapter_bias): the adapter "
+                                 "affine is built for bf16 Linears only, a quantized Linear would drop it")
         return mod.hip_linear(x, out, epilogue=epilogue, residual=residual, partner=partner, norm=norm)
     if isinstance(mod, nn.Linear):
         if partner is not None and not (isinstance(partner, nn.Linear) and not hasattr(partner, "hip_linear")):
             raise ParrotHipError("SwiGLU partner must be the same Linear class")
         return ops.bf16_linear(mod.weight.data, x, out, bias=None if mod.bias is None else mod.bias.data,
                                epilogue=epilogue, residual=residual,
-                               weight2=None if partner is None else partner.weight.data, norm=norm)
+                               weight2=None if partner is None else partner.weight.data, norm=norm, adapter=adapter)
     raise ParrotHipError(f"no HIP kernel for Linear class {type(mod).__name__}")
+
+
+def _adapter_v2(mod: nn.Module, partner: Optional[nn.Module]) -> Optional[ops.Adapter]:
+    """The adapter-v2 vectors (adapter_v2.py) of a Linear and its SwiGLU partner, None for a plain Linear."""
+    names = ("adapter_scale", "adapter_bias")
+    if not any(hasattr(m, n) for m in (mod, partner) if m is not None for n in names):
+        return None
+
+    def vec(m, n):
+        p = getattr(m, n, None) if m is not None else None
+        return None if p is None else p.data
+
+    return ops.Adapter(vec(mod, "adapter_scale"), vec(mod, "adapter_bias"), vec(partner, "adapter_scale"), vec(partner, "adapter_bias"))
 
 
 def _norm(mod: nn.Module, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -340,11 +357,27 @@ class CausalSelfAttention(nn.Module):
         kernel (one launch); several rows (prefill) take rope_kvappend + attn_decode over all rows."""
         c = self.config
         _linear(self.attn, x, ws.qkv, norm=norm)
+        prefix = self.adapter_prefix()
         if ws.M == 1 and not rope_local and c.q_per_kv <= ops.FUSED_ATTN_MAX_Q_PER_KV:
+            if prefix is not None:  # LLaMA-Adapter layer (adapter.py): the gated prefix term inside the same launch
+                return ops.attn_fused_decode_adapter(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,
+                                                     c.q_per_kv, c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y, prefix)
             return ops.attn_fused_decode(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,
                                          c.q_per_kv, c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
         ops.rope_kvappend(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, c.n_query_groups, c.q_per_kv, c.head_size, S,
                           ws.q, k_cache, v_cache, rope_local)
+        y = self._attend_rows(ws, pos, S, k_cache, v_cache, nsplit)
+        if prefix is not None:
+            ops.attn_adapter_prefix(ws.q, c.n_query_groups, c.q_per_kv, c.head_size, y, prefix)
+        return y
+
+    def adapter_prefix(self) -> Optional[ops.AdapterPrefix]:
+        """The LLaMA-Adapter prefix of this layer (adapter.py); a plain layer has none."""
+        return None
+
+    def _attend_rows(self, ws: Workspace, pos: torch.Tensor, S: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                     nsplit: int) -> torch.Tensor:
+        c = self.config
         if (ATTN_PREFILL_MFMA and getattr(ws, "pos_is_zero", False) and ops.ATTN_PREFILL_MIN_ROWS <= ws.M <= S
                 and c.head_size in (32, 64, 128)):
             # a prompt that starts at position 0 (no ring wrap inside the call): flash attention on the matrix cores

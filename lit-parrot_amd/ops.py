@@ -85,9 +85,25 @@ def _norm_arg(norm: Optional[Norm], K: int):
     return None if norm is None else C.byref(norm.c_struct(K))
 
 
+class Adapter:
+    """The adapter-v2 vectors of a Linear (``adapter_scale`` / ``adapter_bias``, lit_gpt/adapter_v2.py:34-53) and of its SwiGLU
+    partner: out = epilogue(scale * (bf16(acc + bias) + adapter_bias)), every step rounded to bf16 (``parrot_adapter_t``)."""
+
+    __slots__ = ("scale", "bias", "scale2", "bias2")
+
+    def __init__(self, scale: Optional[torch.Tensor], bias: Optional[torch.Tensor], scale2: Optional[torch.Tensor] = None,
+                 bias2: Optional[torch.Tensor] = None) -> None:
+        self.scale, self.bias, self.scale2, self.bias2 = scale, bias, scale2, bias2
+
+    def c_struct(self, N: int):
+        v = [_opt_vec(None if t is None else t.reshape(-1), N, f"adapter {nm}")
+             for t, nm in ((self.scale, "scale"), (self.bias, "bias"), (self.scale2, "scale2"), (self.bias2, "bias2"))]
+        return _hip.ParrotAdapter(*(ptr(t) for t in v))
+
+
 # ------------------------------------------------------------------------------------------------ linears
 def bf16_linear(weight: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, bias=None, epilogue=EPI_NONE,
-                residual=None, weight2=None, norm: Optional[Norm] = None) -> torch.Tensor:
+                residual=None, weight2=None, norm: Optional[Norm] = None, adapter: Optional[Adapter] = None) -> torch.Tensor:
     _rows(x, "bf16_linear"), _rows(out, "bf16_linear")
     x, norm = _prenorm(x, norm)
     N, K = weight.shape
@@ -95,6 +111,8 @@ def bf16_linear(weight: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, bia
         raise ParrotHipError("bf16_linear: weight must be contiguous bf16 (out_features, in_features)")
     M = x.shape[0]
     lib = _hip.load()
+    if adapter is not None:
+        return _bf16_linear_adapter(lib, weight, x, out, bias, epilogue, residual, weight2, norm, adapter)
     args = (ptr(weight), ptr(weight2), ptr(x), x.stride(0), M, ptr(_opt_vec(bias, N, "bias")),
             ptr(residual), residual.stride(0) if residual is not None else 0, ptr(out), out.stride(0), N, K,
             epilogue, _norm_arg(norm, K))
@@ -104,6 +122,25 @@ def bf16_linear(weight: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, bia
         n = lib.parrot_gemm_workspace_floats(M, N, K, 0, epilogue)
         ws = torch.empty((n,), dtype=torch.float32, device=x.device) if n > 0 else None
         check(lib.parrot_bf16_gemm(*args, ptr(ws), stream()), "parrot_bf16_gemm")
+    return out
+
+
+def _bf16_linear_adapter(lib, weight, x, out, bias, epilogue, residual, weight2, norm, adapter: Adapter) -> torch.Tensor:
+    """Adapter-v2 Linear: up to GEMV_MAX_ROWS rows the affine is fused into the GEMV's epilogue (one launch, as without it);
+    prompts run the dense GEMM(s) with PARROT_EPI_NONE into scratch, then one element-wise launch (affine -> epilogue)."""
+    N, K = weight.shape
+    M = x.shape[0]
+    ad = C.byref(adapter.c_struct(N))
+    if M <= GEMV_MAX_ROWS:
+        check(lib.parrot_bf16_gemv_adapter(ptr(weight), ptr(weight2), ptr(x), x.stride(0), M, ptr(_opt_vec(bias, N, "bias")),
+                                           ptr(residual), residual.stride(0) if residual is not None else 0, ptr(out), out.stride(0),
+                                           N, K, epilogue, _norm_arg(norm, K), ad, stream()), "parrot_bf16_gemv_adapter")
+        return out
+    t = bf16_linear(weight, x, torch.empty((M, N), dtype=torch.bfloat16, device=x.device), bias=bias, norm=norm)
+    t2 = None if weight2 is None else bf16_linear(weight2, x, torch.empty((M, N), dtype=torch.bfloat16, device=x.device), norm=norm)
+    check(lib.parrot_adapter_epilogue(ptr(t), ptr(t2), N, M, N, ad, epilogue, ptr(residual),
+                                      residual.stride(0) if residual is not None else 0, ptr(out), out.stride(0), stream()),
+          "parrot_adapter_epilogue")
     return out
 
 
@@ -350,6 +387,53 @@ def attn_fused_decode(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n
     check(lib.parrot_attn_fused_decode(ptr(qkv), ptr(cos), ptr(sin), n_elem, ptr(pos), n_groups, q_per_kv, hs, S,
                                        nsplit, ptr(workspace), ptr(tickets), ptr(k_cache), ptr(v_cache), ptr(y),
                                        ATTN_SOFTMAX_MODE, stream()), "parrot_attn_fused_decode")
+    return y
+
+
+class AdapterPrefix:
+    """The LLaMA-Adapter prefix of one layer (lit_gpt/adapter.py:226-254): keys / values (n_groups, aT, hs) bf16 - no RoPE,
+    GQA-native - and the per-head gate (n_head,) bf16 (``gating_factor``)."""
+
+    __slots__ = ("ak", "av", "gate", "aT")
+
+    def __init__(self, ak: torch.Tensor, av: torch.Tensor, gate: torch.Tensor) -> None:
+        if ak.dtype != torch.bfloat16 or av.dtype != torch.bfloat16 or gate.dtype != torch.bfloat16:
+            raise ParrotHipError("adapter prefix: keys, values and gate must be bf16")
+        if ak.dim() != 3 or ak.shape != av.shape or not ak.is_contiguous() or not av.is_contiguous() or not gate.is_contiguous():
+            raise ParrotHipError("adapter prefix: keys / values must be contiguous (n_groups, aT, hs)")
+        self.ak, self.av, self.gate, self.aT = ak, av, gate.view(-1), ak.shape[1]
+
+    def check(self, n_groups: int, q_per_kv: int, hs: int) -> None:
+        if tuple(self.ak.shape) != (n_groups, self.aT, hs) or self.gate.numel() != n_groups * q_per_kv:
+            raise ParrotHipError(f"adapter prefix: keys {tuple(self.ak.shape)} / gate {self.gate.numel()} do not match the layer")
+
+
+def attn_fused_decode_adapter(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_elem: int, pos: torch.Tensor,
+                              k_cache: torch.Tensor, v_cache: torch.Tensor, n_groups: int, q_per_kv: int, hs: int, S: int,
+                              nsplit: int, workspace: torch.Tensor, tickets: torch.Tensor, y: torch.Tensor,
+                              prefix: AdapterPrefix) -> torch.Tensor:
+    """attn_fused_decode plus the gated adapter-prefix term, still one launch."""
+    _rows(qkv, "attn_fused_decode_adapter"), _rows(y, "attn_fused_decode_adapter")
+    if qkv.shape[0] != 1 or tickets.dtype != torch.int32 or tickets.numel() < n_groups * q_per_kv:
+        raise ParrotHipError("attn_fused_decode_adapter: one row, int32 tickets[n_groups] expected")
+    prefix.check(n_groups, q_per_kv, hs)
+    check(_hip.load().parrot_attn_fused_decode_adapter(ptr(qkv), ptr(cos), ptr(sin), n_elem, ptr(pos), n_groups, q_per_kv, hs, S,
+                                                       nsplit, ptr(workspace), ptr(tickets), ptr(k_cache), ptr(v_cache), ptr(y),
+                                                       ptr(prefix.ak), ptr(prefix.av), ptr(prefix.gate), prefix.aT,
+                                                       ATTN_SOFTMAX_MODE, stream()), "parrot_attn_fused_decode_adapter")
+    return y
+
+
+def attn_adapter_prefix(q: torch.Tensor, n_groups: int, q_per_kv: int, hs: int, y: torch.Tensor, prefix: AdapterPrefix) -> torch.Tensor:
+    """y[m] += gate * (prefix attention of the roped query rows q[m]) in place, after attn_decode / attn_prefill."""
+    _rows(q, "attn_adapter_prefix"), _rows(y, "attn_adapter_prefix")
+    prefix.check(n_groups, q_per_kv, hs)
+    M = y.shape[0]
+    if q.shape[0] < M or q.shape[1] != n_groups * q_per_kv * hs or not q.is_contiguous():
+        raise ParrotHipError("attn_adapter_prefix: q must hold (M, n_head * hs) contiguous rows")
+    check(_hip.load().parrot_attn_adapter_prefix(ptr(q), M, ptr(prefix.ak), ptr(prefix.av), ptr(prefix.gate), prefix.aT, n_groups,
+                                                 q_per_kv, hs, ptr(y), y.stride(0), ATTN_SOFTMAX_MODE, stream()),
+          "parrot_attn_adapter_prefix")
     return y
 
 
