@@ -227,6 +227,15 @@ int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* 
                              const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit,
                              void* workspace, void* tickets, void* k_cache, void* v_cache, void* y,
                              int softmax_mode, void* stream);
+/* Batched decode: the same step for B independent sequences of one row each (1 <= B <= 8) in ONE launch.  Row b: qkv + b*ldqkv,
+ * position pos[b] (int32[B]), its own RoPE row, ring slot pos[b] % S and causal limit min(pos[b], S-1), caches k/v_cache +
+ * b*kv_bstride (elements), y + b*ldy.  workspace: parrot_attn_workspace_floats(B, ...); tickets: n_tickets >= B * n_head
+ * zero-initialised uint32 (row b owns b*n_head ..; re-armed by the kernel).  Same limits as parrot_attn_fused_decode
+ * (q_per_kv <= 16, hs 32/64/128, else PARROT_EUNSUPPORTED); B = 1 computes what parrot_attn_fused_decode computes.          */
+int parrot_attn_fused_decode_rows(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                  const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                  void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
+                                  int softmax_mode, void* stream);
 /* LLaMA-Adapter prefix attention (lit_gpt/adapter.py:226-254) in the same launch: ak / av [n_groups][aT][hs] bf16 (the
  * prefix keys / values: no RoPE), gate [n_head] bf16 (gating_factor), 1 <= aT <= 64.  The workgroup that writes y attends
  * every roped query head to all aT prefix keys (own softmax, scale 1/sqrt(hs)) and writes
@@ -244,6 +253,9 @@ int parrot_attn_adapter_prefix(const void* q, int M, const void* ak, const void*
  * x[m] = wte[tokens[(pos ? *pos : 0) + m]]   (lit_gpt/model.py:99)                    */
 int parrot_embedding(const void* wte, int d, const int64_t* tokens, const int32_t* pos, int M,
                      void* out, int ldo, void* stream);
+/* batched decode: x[b] = wte[tokens[b*ld_tokens + (pos ? pos[b] : 0)]] for 1 <= B <= 8 sequences                      */
+int parrot_embedding_rows(const void* wte, int d, const int64_t* tokens, int ld_tokens, const int32_t* pos, int B, void* out, int ldo,
+                          void* stream);
 /* greedy step of generate() (generate/base.py:136-153 with top_k=1):
  * tokens[*pos + 1] = argmax(logits) (lowest index on ties); then *pos += 1.          */
 /* ---- GPTQ quantiser, the column loop of one 128-column block (quantize/gptq.py:397-431) -------------------------
@@ -274,6 +286,14 @@ int parrot_argmax_advance(const void* logits, int V, int64_t* tokens, int32_t* p
  * tests).  torch.multinomial's validity checks (two host syncs per token) are not reproduced.                                 */
 int parrot_topk_sample(const void* logits, int V, float temperature, int top_k, const void* noise_exp1, void* probs_out,
                        int64_t* tokens, int32_t* pos, void* stream);
+/* Batched decode, 1 <= B <= 8 sequences: the greedy / sampling step above on row b of logits [B][ldl] (and of noise [B][V]) with
+ * tokens [B][ldt], pos int32[B], end int32[B]: tokens[b][pos[b] + 1] = the row's token, pos[b] += 1 - bit for bit the one-row
+ * arithmetic - unless row b is frozen: pos[b] + 1 >= min(end[b], ldt), or eos_id >= 0 and tokens[b][pos[b]] == eos_id
+ * (no write, no advance).                                                                                              */
+int parrot_argmax_advance_rows(const void* logits, int V, int ldl, int B, int64_t* tokens, int ldt, int32_t* pos, const int32_t* end,
+                               int eos_id, void* stream);
+int parrot_topk_sample_rows(const void* logits, int V, int ldl, int B, float temperature, int top_k, const void* noise_exp1,
+                            int64_t* tokens, int ldt, int32_t* pos, const int32_t* end, int eos_id, void* stream);
 
 /* ---- stream engine: ONE launch per decode token ------------------------------------------------------------
  * The whole token (generate/base.py:131-153 for one iteration: embedding, every Block of lit_gpt/model.py:158-180,

@@ -98,6 +98,7 @@ SIGNATURES = {
     "parrot_attn_workspace_floats": (_i64, [_i, _i, _i, _i]),
     "parrot_attn_decode": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_fused_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "parrot_attn_fused_decode_rows": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _i, _vp]),
     "parrot_attn_fused_decode_adapter": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_adapter_prefix": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "parrot_attn_prefill_scratch_elems": (_i64, [_i, _i, _i]),
@@ -113,10 +114,13 @@ SIGNATURES = {
     "parrot_eng_lds_total": (_i64, [_i, _i, _i, _i]),
     "parrot_eng_step": (_i, [C.POINTER(EngState), _vp]),
     "parrot_embedding": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "parrot_embedding_rows": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "parrot_gptq_block": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "parrot_stop_check": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "parrot_argmax_advance": (_i, [_vp, _i, _vp, _vp, _vp]),
     "parrot_topk_sample": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "parrot_argmax_advance_rows": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    "parrot_topk_sample_rows": (_i, [_vp, _i, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -502,14 +502,23 @@ attn_adapter_prefix_kernel(const bf16_t* __restrict__ q, int n_head, AdapterAttn
     }
 }
 
+// Batched decode (parrot_attn_fused_decode_rows): B independent sequences, one row each.  Row b reads qkv + b * ldqkv, its
+// own position pos[b], its own caches at + b * kv_bstride, writes y + b * ldy, and owns the workspace slice and the n_head
+// tickets from b * n_head on.  The row index is folded into grid.z (b * chunks + chunk).
+struct AttnRowsArgs {
+    int ldqkv, ldy;
+    int64_t kv_bstride;
+};
+
 // AD: the LLaMA-Adapter prefix term is added by the workgroup that writes y (AD = false is the plain kernel)
-template <int HS, int HQ, int WAVES, bool PM = false, bool AD = false>  // PM: "softmax_mode 1", see attn_decode_kernel
+// ROWS: the batched-decode instantiation; with ROWS = false `rows` is never read and the kernel is the one-row kernel
+template <int HS, int HQ, int WAVES, bool PM = false, bool AD = false, bool ROWS = false>  // PM: "softmax_mode 1", see attn_decode_kernel
 __global__ void __launch_bounds__(WAVES * 64)
 attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restrict__ rope_cos,
                          const __half* __restrict__ rope_sin, int n_elem, const int32_t* __restrict__ pos_ptr,
                          bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache, int n_groups, int q_per_kv, int S,
                          int nsplit, float* __restrict__ ws, unsigned int* __restrict__ tickets, bf16_t* __restrict__ y,
-                         unsigned long long* dbg, AdapterAttnArgs aa) {
+                         unsigned long long* dbg, AdapterAttnArgs aa, AttnRowsArgs rows) {
     constexpr int LPR = HS / 8;
     constexpr int RPW = 64 / LPR;
     attn_stamp(dbg, 0);
@@ -519,11 +528,27 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     __shared__ __attribute__((aligned(16))) bf16_t sh_kv[2][HS];  // roped k_new, v_new as stored in the cache
     __shared__ int sh_last;
 
+    const int n_head = n_groups * q_per_kv;
+    int chunk = blockIdx.z;  // chunk of the group's query heads
+    unsigned int* ticket;
+    if constexpr (ROWS) {
+        const int nchunk = (q_per_kv + HQ - 1) / HQ;
+        const int b = blockIdx.z / nchunk;
+        chunk = blockIdx.z - b * nchunk;
+        qkv += (int64_t)b * rows.ldqkv;
+        pos_ptr += b;
+        k_cache += b * rows.kv_bstride;
+        v_cache += b * rows.kv_bstride;
+        ws += (int64_t)b * n_head * nsplit * (HS + 2);
+        y += (int64_t)b * rows.ldy;
+        ticket = &tickets[b * n_head + blockIdx.x * nchunk + chunk];
+    } else {
+        ticket = &tickets[blockIdx.x * gridDim.z + blockIdx.z];
+    }
     const int g = blockIdx.x, split = blockIdx.y;
-    const int h0 = blockIdx.z * HQ;  // this workgroup's chunk of the group's query heads (GQA: chunks run in parallel)
+    const int h0 = chunk * HQ;  // this workgroup's chunk of the group's query heads (GQA: chunks run in parallel)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, dl = lane % LPR;
-    const int n_head = n_groups * q_per_kv;
     const int pos = pos_ptr[0];
     const int n_valid = min(pos + 1, S);
     const int slot_new = pos % S;
@@ -581,7 +606,7 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     __syncthreads();
     attn_stamp(dbg, 1);
     // ---- KV append by the workgroup that owns the new slot
-    if (blockIdx.z == 0 && slot_new >= s_begin && slot_new < s_begin + per && threadIdx.x < 2 * LPR) {
+    if (chunk == 0 && slot_new >= s_begin && slot_new < s_begin + per && threadIdx.x < 2 * LPR) {
         const int which = threadIdx.x / LPR, c = threadIdx.x % LPR;
         bf16_t* dst = (which ? v_cache : k_cache) + ((int64_t)g * S + slot_new) * HS;
         reinterpret_cast<uint4*>(dst)[c] = reinterpret_cast<const uint4*>(sh_kv[which])[c];
@@ -748,9 +773,9 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned int t = __hip_atomic_fetch_add(&tickets[g * gridDim.z + blockIdx.z], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         sh_last = (t == (unsigned int)(nsplit - 1));
-        if (sh_last) __hip_atomic_store(&tickets[g * gridDim.z + blockIdx.z], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+        if (sh_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
     }
     __syncthreads();
     if (!sh_last) return;
@@ -779,24 +804,27 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     }
 }
 
-template <int HS, bool AD = false>
+// B > 0 (ROWS): B sequences of one row each, strides in `rows`
+template <int HS, bool AD = false, bool ROWS = false>
 static int attn_fused_launch(const void* qkv, const void* cosp, const void* sinp, int n_elem, const int32_t* pos,
                              void* k_cache, void* v_cache, int n_groups, int q_per_kv, int S, int nsplit, void* ws,
-                             void* tickets, void* y, int softmax_mode, hipStream_t st, AdapterAttnArgs aa = {}) {
+                             void* tickets, void* y, int softmax_mode, hipStream_t st, AdapterAttnArgs aa = {},
+                             int B = 1, AttnRowsArgs rows = {}) {
     const int hq = q_per_kv == 1 ? 1 : (q_per_kv == 2 ? 2 : 4);
     // 16 waves when a split holds more keys than 4 waves cover in two steps
     const int per = (S + nsplit - 1) / nsplit;
     const bool wide = per > 2 * kAttnWaves * (64 / (HS / 8));
-    const dim3 grid(n_groups, nsplit, (q_per_kv + hq - 1) / hq), block((wide ? 16 : kAttnWaves) * 64);
+    const dim3 grid(n_groups, nsplit, B * ((q_per_kv + hq - 1) / hq)), block((wide ? 16 : kAttnWaves) * 64);
+    const int kid = ROWS ? K_ATTN_FUSED_ROWS : K_ATTN_FUSED;
 #define PARROT_FUSED_GO(HQV, WV)                                                                                            \
     do {                                                                                                                    \
         if (softmax_mode == 1)                                                                                              \
-            return launch(K_ATTN_FUSED, attn_fused_decode_kernel<HS, HQV, 16, true, AD>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
+            return launch(kid, attn_fused_decode_kernel<HS, HQV, 16, true, AD, ROWS>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
                           (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups, \
-                          q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa);         \
-        return launch(K_ATTN_FUSED, attn_fused_decode_kernel<HS, HQV, WV, false, AD>, grid, block, 0, st, (const bf16_t*)qkv, \
+                          q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa, rows);   \
+        return launch(kid, attn_fused_decode_kernel<HS, HQV, WV, false, AD, ROWS>, grid, block, 0, st, (const bf16_t*)qkv, \
                       (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups,   \
-                      q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa);             \
+                      q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa, rows);       \
     } while (0)
     if (wide) {
         if (q_per_kv == 1) PARROT_FUSED_GO(1, 16);
@@ -917,6 +945,42 @@ int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* 
                              void* k_cache, void* v_cache, void* y, int softmax_mode, void* stream) {
     return attn_fused_entry(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache,
                             v_cache, y, softmax_mode, nullptr, stream);
+}
+
+int parrot_attn_fused_decode_rows(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                  const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                  void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
+                                  int softmax_mode, void* stream) {
+    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "attn_fused_decode_rows: B=%d (1 .. %d)", B, kMaxDecodeRows);
+    {
+        const int rc = check_softmax_mode("attn_fused_decode_rows", softmax_mode, S, nsplit);
+        if (rc != PARROT_OK) return rc;
+    }
+    PARROT_REQUIRE(qkv && pos && k_cache && v_cache && y, "attn_fused_decode_rows: null pointer");
+    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1, "attn_fused_decode_rows: bad shape");
+    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "attn_fused_decode_rows: at most %d query heads per group (got %d)", kFusedMaxQ, q_per_kv);
+    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "attn_fused_decode_rows: head size %d not built (32, 64, 128)", hs);
+    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "attn_fused_decode_rows: bad n_elem=%d", n_elem);
+    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "attn_fused_decode_rows: rope tables missing");
+    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "attn_fused_decode_rows: nsplit out of range");
+    const int n_head = n_groups * q_per_kv;
+    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "attn_fused_decode_rows: workspace and tickets required when nsplit > 1");
+    PARROT_REQUIRE(!tickets || n_tickets >= B * n_head, "attn_fused_decode_rows: %d tickets, B * n_head = %d needed", n_tickets, B * n_head);
+    PARROT_REQUIRE(ldqkv >= n_groups * (q_per_kv + 2) * hs && ldqkv % 8 == 0, "attn_fused_decode_rows: ldqkv=%d too small or not a multiple of 8", ldqkv);
+    PARROT_REQUIRE(ldy >= n_head * hs, "attn_fused_decode_rows: ldy=%d too small", ldy);
+    PARROT_REQUIRE(kv_bstride >= (int64_t)n_groups * S * hs && kv_bstride % 8 == 0,
+                   "attn_fused_decode_rows: kv_bstride=%lld below n_groups * S * hs or not a multiple of 8", (long long)kv_bstride);
+    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "attn_fused_decode_rows: 16-byte alignment");
+    const AttnRowsArgs rows{ldqkv, ldy, kv_bstride};
+    hipStream_t st = (hipStream_t)stream;
+    switch (hs) {
+        case 32: return attn_fused_launch<32, false, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
+                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
+        case 64: return attn_fused_launch<64, false, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
+                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
+        default: return attn_fused_launch<128, false, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
+                                                            nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
+    }
 }
 
 // prefix K/V, gate and aT of the two adapter entry points

@@ -14,12 +14,29 @@ embedding_kernel(const uint4* __restrict__ wte, int d16, const int64_t* __restri
         out[(int64_t)m * ldo16 + c] = wte[tok * d16 + c];
 }
 
+// batched decode: x[b] = wte[tokens[b * ld_tokens + (pos ? pos[b] : 0)]], one row per sequence
+__global__ void __launch_bounds__(256)
+embedding_rows_kernel(const uint4* __restrict__ wte, int d16, const int64_t* __restrict__ tokens, int ld_tokens,
+                      const int32_t* __restrict__ pos, uint4* __restrict__ out, int ldo16) {
+    const int b = blockIdx.y;
+    const int64_t tok = tokens[(int64_t)b * ld_tokens + (pos ? pos[b] : 0)];
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < d16; c += gridDim.x * blockDim.x)
+        out[(int64_t)b * ldo16 + c] = wte[tok * d16 + c];
+}
+
+// Batched decode: row b of the sampling step is frozen (no token write, no advance) once its next position would reach end[b]
+// (or the row of its token buffer) or its last written token is eos_id (-1: none).  A frozen row re-runs its own position in
+// the next step, which rewrites the same K/V slot with the same values.  Block-uniform: every thread reads the same words.
+__device__ __forceinline__ bool decode_row_frozen(const int64_t* tokens_row, int ldt, int pos, int end, int eos_id) {
+    return pos + 1 >= end || pos + 1 >= ldt || (eos_id >= 0 && tokens_row[pos] == (int64_t)eos_id);
+}
+
 // generate/base.py:136-153 with temperature > 0 and top_k = 1: the sampled token is the arg-max of the logits.
 // (The reference draws from a one-hot multinomial; with tied maxima it picks one of them at random, here the
 // lowest index wins.)  Single workgroup; then the loop state advances: tokens[pos+1] = best, pos += 1.
 constexpr int kArgmaxThreads = 1024;
-__global__ void __launch_bounds__(kArgmaxThreads)
-argmax_advance_kernel(const bf16_t* __restrict__ logits, int V, int vec, int64_t* __restrict__ tokens, int32_t* __restrict__ pos_ptr) {
+// the arg-max of one row of logits; the result is valid in thread 0 (0x7fffffff: no element)
+__device__ __forceinline__ int argmax_row(const bf16_t* __restrict__ logits, int V, int vec) {
     __shared__ float sv[kArgmaxThreads / 64];
     __shared__ int si[kArgmaxThreads / 64];
     float best = -INFINITY;
@@ -82,9 +99,32 @@ argmax_advance_kernel(const bf16_t* __restrict__ logits, int V, int vec, int64_t
                 best = sv[w];
                 bi = si[w];
             }
+    }
+    return bi;
+}
+
+__global__ void __launch_bounds__(kArgmaxThreads)
+argmax_advance_kernel(const bf16_t* __restrict__ logits, int V, int vec, int64_t* __restrict__ tokens, int32_t* __restrict__ pos_ptr) {
+    const int bi = argmax_row(logits, V, vec);
+    if (threadIdx.x == 0) {
         const int pos = pos_ptr[0];
         tokens[pos + 1] = (bi == 0x7fffffff) ? 0 : bi;
         pos_ptr[0] = pos + 1;
+    }
+}
+
+// batched decode: one workgroup per row b of logits [B][ldl]; tokens [B][ldt], pos [B], end [B]
+__global__ void __launch_bounds__(kArgmaxThreads)
+argmax_advance_rows_kernel(const bf16_t* __restrict__ logits, int V, int ldl, int vec, int64_t* __restrict__ tokens, int ldt,
+                           int32_t* __restrict__ pos, const int32_t* __restrict__ end, int eos_id) {
+    const int b = blockIdx.x;
+    int64_t* trow = tokens + (int64_t)b * ldt;
+    const int p = pos[b];
+    if (decode_row_frozen(trow, ldt, p, end[b], eos_id)) return;
+    const int bi = argmax_row(logits + (int64_t)b * ldl, V, vec);
+    if (threadIdx.x == 0) {
+        trow[p + 1] = (bi == 0x7fffffff) ? 0 : bi;
+        pos[b] = p + 1;
     }
 }
 
@@ -183,10 +223,10 @@ struct SampleElems {
     }
 };
 
+// the sampled index of one row; valid in thread 0 (0x7fffffff: no element)
 template <int NCH>
-__global__ void __launch_bounds__(kSampleThreads)
-topk_sample_kernel(const bf16_t* __restrict__ logits, int V, float inv_temperature, int top_k, const bf16_t* __restrict__ noise,
-                   bf16_t* __restrict__ probs_out, int64_t* __restrict__ tokens, int32_t* __restrict__ pos_ptr) {
+__device__ __forceinline__ int topk_sample_row(const bf16_t* __restrict__ logits, int V, float inv_temperature, int top_k,
+                                               const bf16_t* __restrict__ noise, bf16_t* __restrict__ probs_out) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t sel[2];
     __shared__ float redf[kSampleThreads / 64];
@@ -282,9 +322,36 @@ topk_sample_kernel(const bf16_t* __restrict__ logits, int V, float inv_temperatu
                 best = redf[w];
                 bi = redi[w];
             }
+    }
+    return bi;
+}
+
+template <int NCH>
+__global__ void __launch_bounds__(kSampleThreads)
+topk_sample_kernel(const bf16_t* __restrict__ logits, int V, float inv_temperature, int top_k, const bf16_t* __restrict__ noise,
+                   bf16_t* __restrict__ probs_out, int64_t* __restrict__ tokens, int32_t* __restrict__ pos_ptr) {
+    const int bi = topk_sample_row<NCH>(logits, V, inv_temperature, top_k, noise, probs_out);
+    if (threadIdx.x == 0) {
         const int pos = pos_ptr[0];
         tokens[pos + 1] = (bi == 0x7fffffff) ? 0 : bi;
         pos_ptr[0] = pos + 1;
+    }
+}
+
+// batched decode: one workgroup per row b of logits [B][ldl] and noise [B][V]; tokens [B][ldt], pos [B], end [B]
+template <int NCH>
+__global__ void __launch_bounds__(kSampleThreads)
+topk_sample_rows_kernel(const bf16_t* __restrict__ logits, int V, int ldl, float inv_temperature, int top_k,
+                        const bf16_t* __restrict__ noise, int64_t* __restrict__ tokens, int ldt, int32_t* __restrict__ pos,
+                        const int32_t* __restrict__ end, int eos_id) {
+    const int b = blockIdx.x;
+    int64_t* trow = tokens + (int64_t)b * ldt;
+    const int p = pos[b];
+    if (decode_row_frozen(trow, ldt, p, end[b], eos_id)) return;
+    const int bi = topk_sample_row<NCH>(logits + (int64_t)b * ldl, V, inv_temperature, top_k, noise + (int64_t)b * V, nullptr);
+    if (threadIdx.x == 0) {
+        trow[p + 1] = (bi == 0x7fffffff) ? 0 : bi;
+        pos[b] = p + 1;
     }
 }
 
@@ -363,6 +430,54 @@ int parrot_argmax_advance(const void* logits, int V, int64_t* tokens, int32_t* p
     const int vec = (V >= 8 && aligned16(logits)) ? 1 : 0;
     return launch(K_ARGMAX, argmax_advance_kernel, dim3(1), dim3(kArgmaxThreads), 0, (hipStream_t)stream,
                   (const bf16_t*)logits, V, vec, tokens, pos);
+}
+
+int parrot_embedding_rows(const void* wte, int d, const int64_t* tokens, int ld_tokens, const int32_t* pos, int B, void* out, int ldo,
+                          void* stream) {
+    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "embedding_rows: B=%d (1 .. %d)", B, kMaxDecodeRows);
+    PARROT_REQUIRE(wte && tokens && out, "embedding_rows: null pointer");
+    PARROT_REQUIRE(ld_tokens >= 1, "embedding_rows: ld_tokens=%d", ld_tokens);
+    PARROT_REQUIRE(d >= 8 && d % 8 == 0 && ldo % 8 == 0 && ldo >= d,
+                   "embedding_rows: d and ldo must be multiples of 8 (d=%d ldo=%d)", d, ldo);
+    PARROT_REQUIRE(aligned16(wte) && aligned16(out), "embedding_rows: pointers must be 16-byte aligned");
+    const int d16 = d / 8;
+    return launch(K_EMBEDDING_ROWS, embedding_rows_kernel, dim3((d16 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream,
+                  (const uint4*)wte, d16, tokens, ld_tokens, pos, (uint4*)out, ldo / 8);
+}
+
+// the argument checks of the two batched sampling steps
+static int check_sample_rows(const char* who, const void* logits, int V, int ldl, int B, const void* tokens, int ldt, const void* pos,
+                             const void* end, int eos_id) {
+    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "%s: B=%d (1 .. %d)", who, B, kMaxDecodeRows);
+    PARROT_REQUIRE(logits && tokens && pos && end, "%s: null pointer", who);
+    PARROT_REQUIRE(V >= 1 && ldl >= V && ldt >= 2, "%s: bad shape V=%d ldl=%d ldt=%d", who, V, ldl, ldt);
+    PARROT_REQUIRE(eos_id >= -1, "%s: eos_id=%d (-1: none)", who, eos_id);
+    return PARROT_OK;
+}
+
+int parrot_argmax_advance_rows(const void* logits, int V, int ldl, int B, int64_t* tokens, int ldt, int32_t* pos, const int32_t* end,
+                               int eos_id, void* stream) {
+    const int rc = check_sample_rows("argmax_advance_rows", logits, V, ldl, B, tokens, ldt, pos, end, eos_id);
+    if (rc != PARROT_OK) return rc;
+    const int vec = (V >= 8 && aligned16(logits) && ldl % 8 == 0) ? 1 : 0;
+    return launch(K_ARGMAX_ROWS, argmax_advance_rows_kernel, dim3(B), dim3(kArgmaxThreads), 0, (hipStream_t)stream,
+                  (const bf16_t*)logits, V, ldl, vec, tokens, ldt, pos, end, eos_id);
+}
+
+int parrot_topk_sample_rows(const void* logits, int V, int ldl, int B, float temperature, int top_k, const void* noise_exp1,
+                            int64_t* tokens, int ldt, int32_t* pos, const int32_t* end, int eos_id, void* stream) {
+    const int rc = check_sample_rows("topk_sample_rows", logits, V, ldl, B, tokens, ldt, pos, end, eos_id);
+    if (rc != PARROT_OK) return rc;
+    PARROT_REQUIRE(noise_exp1, "topk_sample_rows: null pointer");
+    PARROT_REQUIRE(temperature > 0.f, "topk_sample_rows: temperature must be positive (got %g)", (double)temperature);
+    // as parrot_topk_sample, every row in registers when they all are 16-byte aligned
+    const bool vec = V % 8 == 0 && ldl % 8 == 0 && aligned16(logits);
+#define PARROT_SAMPLE_ROWS_GO(NCHV)                                                                                               \
+    return launch(K_TOPK_SAMPLE_ROWS, topk_sample_rows_kernel<NCHV>, dim3(B), dim3(kSampleThreads), 0, (hipStream_t)stream,      \
+                  (const bf16_t*)logits, V, ldl, 1.0f / temperature, top_k, (const bf16_t*)noise_exp1, tokens, ldt, pos, end, eos_id)
+    if (vec && V <= 8192 * 4) PARROT_SAMPLE_ROWS_GO(4);
+    PARROT_SAMPLE_ROWS_GO(0);
+#undef PARROT_SAMPLE_ROWS_GO
 }
 
 }  // extern "C"

@@ -57,6 +57,9 @@ inline int check_linear_args(const char* who, const void* W, const void* W2, con
     return PARROT_OK;
 }
 
+// batched decode (the *_rows entry points): B independent sequences of one row each, 1 <= B <= kMaxDecodeRows
+constexpr int kMaxDecodeRows = 8;
+
 // ---------------------------------------------------------------- kernel ids (profiling sink)
 enum KernelId : int {
     K_W4_GEMV = 0,
@@ -95,6 +98,10 @@ enum KernelId : int {
     K_TOPK_SAMPLE,
     K_ADAPTER_EPI,
     K_ATTN_ADAPTER_PREFIX,
+    K_EMBEDDING_ROWS,
+    K_ARGMAX_ROWS,
+    K_TOPK_SAMPLE_ROWS,
+    K_ATTN_FUSED_ROWS,
     K_COUNT
 };
 

@@ -20,7 +20,7 @@ draws the same tokens as those ops do on this device (tests/test_model_gpu.py::t
 The prompt is prefilled in one multi-row pass (same kernels, M = T rows) that computes only the last row of lm_head
 (the reference computes all T rows and discards T-1 of them, :135-136).
 """
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -162,15 +162,14 @@ RELEASE_REFERENCE_BUFFERS = True
 MAX_SESSIONS_PER_MODEL = 4  # captured steps kept per model (keyed by window, greedy / sampling parameters), least recently used first out
 
 
-def _session(model: GPT, max_seq_length: int, max_tokens: int, greedy: bool,
-             sampler: Optional[Tuple[float, Optional[int]]] = None) -> DecodeSession:
-    cache: Dict[Tuple, DecodeSession] = model.__dict__.setdefault("_decode_sessions", {})
-    sampler = None if greedy else sampler
-    key = (max_seq_length, greedy, sampler)
+def _cached_session(model: GPT, key: Tuple, max_tokens: int, make: Callable):
+    """The session under ``key`` in the model's LRU cache of captured steps (single-sequence and batched sessions alike), rebuilt
+    by ``make()`` when it is missing, too short, or no longer holds the model's current KV caches."""
+    cache: Dict[Tuple, object] = model.__dict__.setdefault("_decode_sessions", {})
     sess = cache.get(key)
     stale = (
         sess is None
-        or sess.tokens.numel() < max_tokens + 1
+        or sess.tokens.shape[-1] < max_tokens + 1
         or not model.kv_caches
         or model.kv_caches[0][0].data_ptr() != sess.caches[0][0].data_ptr()
     )
@@ -179,11 +178,18 @@ def _session(model: GPT, max_seq_length: int, max_tokens: int, greedy: bool,
         sess = None  # (the old session's buffers go before the new one's are allocated)
         while len(cache) >= MAX_SESSIONS_PER_MODEL:  # a caller that varies temperature / top_k per request must not pile up graphs
             cache.pop(next(iter(cache)))
-        sess = DecodeSession(model, max_seq_length, max_tokens, greedy, sampler=sampler)
+        sess = make()
     else:
         cache.pop(key)  # (re-inserted below: the dict's order is the order of last use)
     cache[key] = sess
     return sess
+
+
+def _session(model: GPT, max_seq_length: int, max_tokens: int, greedy: bool,
+             sampler: Optional[Tuple[float, Optional[int]]] = None) -> DecodeSession:
+    sampler = None if greedy else sampler
+    return _cached_session(model, (max_seq_length, greedy, sampler), max_tokens,
+                           lambda: DecodeSession(model, max_seq_length, max_tokens, greedy, sampler=sampler))
 
 
 @torch.no_grad()
@@ -232,4 +238,182 @@ def generate(
         i = n_new
     out = sess.tokens[: T + i].to(dtype).clone()
     sess.check_error()  # a bounded in-launch wait gave up (e.g. fewer CUs than resident workgroups): fail loudly
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ batched decode
+class BatchDecodeSession:
+    """Static buffers + captured graph of the batched step: B independent sequences (1 <= B <= 8), one row each.
+
+        tokens  int64[B][L]   row b: prompt b, then its sampled tokens
+        pos     int32[B]      position of row b's token being decoded
+        end     int32[B]      row b stops before position end[b] (max_returned_tokens)
+
+    One step embeds ``tokens[b, pos[b]]`` for every row, runs every block over the B rows (each Linear's weights are streamed once
+    per 4 rows - int4 / NF4 - or per 2 rows - bf16 -, one attention launch per layer for all rows, each row in its own cache slice
+    ``kv_caches[i][0][b]``), lm_head on all rows and one sampling launch that advances every row that is not frozen (at ``end``
+    or after ``eos_id``).  The stream engine is batch-1: this step is always the multi-launch one."""
+
+    def __init__(self, model: GPT, B: int, max_seq_length: int, max_tokens: int, greedy: bool,
+                 sampler: Optional[Tuple[float, Optional[int]]] = None, eos_id: int = -1, use_graph: bool = True) -> None:
+        self.model, self.B, self.S, self.greedy, self.eos_id = model, B, max_seq_length, greedy, eos_id
+        self.sampler = None if greedy else sampler
+        dev = model.transformer.wte.weight.device
+        if dev.type != "cuda":
+            raise ParrotHipError("generate_batch() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+        self.device = dev
+        self.tokens = torch.zeros((B, max_tokens + 1), dtype=torch.int64, device=dev)
+        self.pos = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.end = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.ws = model.workspace(B, dev, B, rows_are_sequences=True)
+        V = model.config.padded_vocab_size
+        self.first_logits = torch.empty((B, V), dtype=torch.bfloat16, device=dev)  # the prompts' last rows
+        self.noise = torch.empty((B, V), dtype=torch.bfloat16, device=dev) if self.sampler is not None else None
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.use_graph = use_graph
+        if model.rope_cache is None:
+            model.rope_cache = model.build_rope_cache(self.tokens)
+        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != B:
+            model.kv_caches = model.build_kv_caches(self.tokens, max_seq_length, model.rope_cache[0].size(-1))
+        self.caches = list(model.kv_caches)  # (B, n_groups, S, hs) per layer
+        if RELEASE_REFERENCE_BUFFERS:
+            for m in model.modules():
+                if hasattr(m, "release_reference"):
+                    m.release_reference()
+
+    def sample(self, logits: torch.Tensor, eos_id: int) -> None:
+        """Row b: ``tokens[b, pos[b] + 1]`` = the token drawn from ``logits[b]``, ``pos[b] += 1``, unless the row is frozen.  The noise
+        of all rows is drawn by one ``exponential_`` call (B = 1 consumes the generator as generate() does)."""
+        if self.greedy:
+            ops.argmax_advance_rows(logits, self.tokens, self.pos, self.end, eos_id)
+            return
+        self.noise.exponential_(1)
+        ops.topk_sample_rows(logits, self.sampler[0], self.sampler[1], self.noise, self.tokens, self.pos, self.end, eos_id)
+
+    def _step(self) -> None:
+        logits = self.model.run_rows(self.ws, self.tokens, self.pos, self.pos, self.S, self.caches, self.model.rope_cache)
+        self.sample(logits, self.eos_id)
+
+    def prefill(self, prompts: Sequence[torch.Tensor], max_returned_tokens: int) -> None:
+        """Each prompt through the multi-row path into its own cache slice; leaves pos[b] = T_b - 1 and the last rows' logits in
+        ``first_logits``."""
+        for b, p in enumerate(prompts):
+            T = p.numel()
+            self.tokens[b, :T].copy_(p)
+            ws = self.model.workspace(T, self.device, 1)
+            ws.pos_is_zero = True  # the prompt starts at position 0 (see DecodeSession.prefill)
+            try:
+                logits = self.model.run_rows(ws, self.tokens[b], None, self.zero_pos, self.S,
+                                             [(k[b], v[b]) for k, v in self.caches], self.model.rope_cache)
+            finally:
+                ws.pos_is_zero = False
+            self.first_logits[b].copy_(logits[0])
+        self.pos.copy_(torch.tensor([p.numel() - 1 for p in prompts], dtype=torch.int32))
+        self.end.fill_(max_returned_tokens)
+
+    def capture(self) -> None:
+        if self.graph is not None or not self.use_graph:
+            return
+        # warm-up outside capture, restoring the loop state afterwards (as DecodeSession.capture)
+        saved = (self.tokens.clone(), self.pos.clone(), [(k.clone(), v.clone()) for k, v in self.caches])
+        rng = torch.cuda.get_rng_state(self.device) if self.sampler is not None else None
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            self._step()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._step()
+        self.graph = graph
+        if rng is not None:
+            torch.cuda.set_rng_state(rng, self.device)
+        self.tokens.copy_(saved[0])
+        self.pos.copy_(saved[1])
+        for (k, v), (k0, v0) in zip(self.caches, saved[2]):
+            k.copy_(k0)
+            v.copy_(v0)
+
+    def step(self) -> None:
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._step()
+
+    def all_frozen(self) -> bool:
+        """One host read of every row's position and last token: True once no row can advance (at ``end`` or after ``eos_id``)."""
+        pos = self.pos.long()
+        state = torch.stack([pos, self.tokens.gather(1, pos.view(-1, 1)).view(-1), self.end.long()]).cpu()
+        return bool(((state[0] + 1 >= state[2]) | (state[1] == self.eos_id)).all())
+
+
+def _batch_prompts(prompts: Union[torch.Tensor, Sequence[torch.Tensor]]) -> List[torch.Tensor]:
+    if isinstance(prompts, torch.Tensor):
+        if prompts.dim() != 2:
+            raise ParrotHipError(f"generate_batch: a tensor of prompts must be (B, T), got shape {tuple(prompts.shape)}")
+        prompts = list(prompts)
+    prompts = list(prompts)
+    for b, p in enumerate(prompts):
+        if not isinstance(p, torch.Tensor) or p.dim() != 1:
+            raise ParrotHipError(f"generate_batch: prompt {b} must be a 1-D token tensor")
+        if p.numel() == 0:
+            raise ParrotHipError(f"generate_batch: prompt {b} is empty")
+    if not 1 <= len(prompts) <= ops.GEMV_MAX_ROWS:
+        raise ParrotHipError(f"generate_batch: {len(prompts)} prompts; the batched step takes 1 to {ops.GEMV_MAX_ROWS} sequences")
+    return prompts
+
+
+@torch.no_grad()
+def generate_batch(
+    model: torch.nn.Module,
+    prompts: Union[torch.Tensor, Sequence[torch.Tensor]],
+    max_returned_tokens: int,
+    max_seq_length: int,
+    *,
+    temperature: float = 1.0,
+    top_k: Optional[int] = None,
+    eos_id: Optional[int] = None,
+) -> List[torch.Tensor]:
+    """``generate()`` for up to 8 prompts at once: row b of the result is what ``generate(model, prompts[b], ...)`` returns - the
+    prompt followed by its generated tokens, at most ``max_returned_tokens`` long, cut before ``eos_id``.  ``prompts``: a list
+    of 1-D token tensors (lengths may differ) or a (B, T) tensor.  Every step decodes all rows in one captured batched pass
+    (BatchDecodeSession), so the weights are read once per pass instead of once per sequence."""
+    prompts = _batch_prompts(prompts)
+    if not isinstance(model, GPT):
+        raise ParrotHipError("generate_batch() drives lit_parrot_amd.GPT models")
+    for p in prompts:  # generate()'s checks, row by row
+        T = p.numel()
+        assert max_returned_tokens > T
+        assert max_seq_length <= model.config.block_size
+        if max_returned_tokens > model.config.block_size:
+            raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
+                                 "positions past the RoPE tables")
+        assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
+    if model.transformer.wte.weight.device.type != "cuda":
+        raise ParrotHipError("generate_batch() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    why = model.batched_decode_unsupported()
+    if why is not None:
+        raise ParrotHipError(f"generate_batch: {why}; use generate() per prompt")
+    B = len(prompts)
+    greedy = top_k == 1 and temperature > 0
+    sampler = None if greedy else (float(temperature), top_k)
+    eos = -1 if eos_id is None else int(eos_id)
+    sess = _cached_session(model, ("batch", B, max_seq_length, greedy, sampler, eos), max_returned_tokens,
+                           lambda: BatchDecodeSession(model, B, max_seq_length, max_returned_tokens, greedy, sampler, eos))
+    sess.prefill([p.to(device=sess.device, dtype=torch.int64) for p in prompts], max_returned_tokens)
+    sess.capture()
+    sess.sample(sess.first_logits, -1)  # the first token of every row is drawn whatever the prompt's last token is
+    for _ in range(max_returned_tokens - min(p.numel() for p in prompts) - 1):
+        if eos_id is not None and sess.all_frozen():  # host sync, as in generate()
+            break
+        sess.step()
+    tokens, pos = sess.tokens.cpu(), sess.pos.cpu()
+    out = []
+    for b, p in enumerate(prompts):
+        n = int(pos[b]) + 1
+        if eos_id is not None and n > p.numel() and int(tokens[b, n - 1]) == eos:
+            n -= 1  # the reference returns idx[:input_pos]: the eos token is not part of the result
+        out.append(sess.tokens[b, :n].to(p.dtype).clone())
     return out

@@ -48,14 +48,17 @@ def norm_class(config: Config):
 
 
 class Workspace:
-    """Every intermediate of ``M`` token rows through the network (allocated once per M)."""
+    """Every intermediate of ``M`` token rows through the network (allocated once per M).
 
-    def __init__(self, config: Config, M: int, device, lm_rows: int) -> None:
+    ``rows_are_sequences``: batched decode - row b is the one new token of sequence b (its own position and KV cache), not
+    position ``pos + b`` of one sequence."""
+
+    def __init__(self, config: Config, M: int, device, lm_rows: int, rows_are_sequences: bool = False) -> None:
         def buf(cols: int, rows: int = M) -> torch.Tensor:
             return torch.empty((rows, cols), dtype=torch.bfloat16, device=device)
 
         c = config
-        self.M, self.lm_rows = M, lm_rows
+        self.M, self.lm_rows, self.rows_are_sequences = M, lm_rows, rows_are_sequences
         self.x, self.t = buf(c.n_embd), buf(c.n_embd)
         self.qkv = buf(c.qkv_size)
         self.q = buf(c.n_head * c.head_size)
@@ -64,7 +67,8 @@ class Workspace:
         self.logits = buf(c.padded_vocab_size, lm_rows)
         self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=device)
         self.side_stream = None  # parallel-residual blocks: the MLP's first Linear runs beside the attention branch
-        self.tickets = torch.zeros((c.n_head,), dtype=torch.int32, device=device)  # fused attention arrival counters
+        # fused attention arrival counters (n_head per sequence)
+        self.tickets = torch.zeros((M * c.n_head if rows_are_sequences else c.n_head,), dtype=torch.int32, device=device)
         self._attn_ws = {}
 
     def attn_ws(self, config: Config, nsplit: int) -> torch.Tensor:
@@ -199,14 +203,31 @@ class GPT(nn.Module):
             for _ in range(c.n_layer)
         ]
 
-    def workspace(self, M: int, device, lm_rows: Optional[int] = None) -> Workspace:
+    def workspace(self, M: int, device, lm_rows: Optional[int] = None, rows_are_sequences: bool = False) -> Workspace:
         lm_rows = M if lm_rows is None else lm_rows
-        key = (M, lm_rows, str(device))
+        key = (M, lm_rows, str(device)) + (("rows",) if rows_are_sequences else ())
         if key not in self._workspaces:
             if len(self._workspaces) > 8:
                 self._workspaces.clear()
-            self._workspaces[key] = Workspace(self.config, M, device, lm_rows)
+            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows_are_sequences)
         return self._workspaces[key]
+
+    def batched_decode_unsupported(self) -> Optional[str]:
+        """Why the batched decode step (one row per sequence, ``Workspace(rows_are_sequences=True)``) cannot run this model,
+        or None when it can."""
+        from .quantize.bnb import InferenceLinear8bitLt
+
+        c = self.config
+        if hasattr(self, "adapter_kv_caches") or any(hasattr(m, "adapter_scale") or hasattr(m, "adapter_bias") for m in self.modules()):
+            return "adapter models decode one sequence at a time (the prefix / adapter-v2 terms are built for one row)"
+        if any(isinstance(m, InferenceLinear8bitLt) for m in self.modules()):
+            return ("LLM.int8 Linears decode one sequence at a time: the multi-row activation quantiser takes the outlier columns "
+                    "of all rows together, so one sequence's output would depend on the others")
+        if c.q_per_kv > ops.FUSED_ATTN_MAX_Q_PER_KV:
+            return f"{c.q_per_kv} query heads per K/V group: the batched attention is built for at most {ops.FUSED_ATTN_MAX_Q_PER_KV}"
+        if c.head_size not in (32, 64, 128):
+            return f"head size {c.head_size}: the batched attention is built for 32, 64 and 128"
+        return None
 
     # ------------------------------------------------------------------------------------------ execution
     def run_rows(self, ws: Workspace, tokens: torch.Tensor, tok_pos: Optional[torch.Tensor], pos: torch.Tensor,
@@ -215,10 +236,16 @@ class GPT(nn.Module):
 
         ``pos`` (device int32[1]) is the position of row 0; ``caches[i]`` are (n_groups, S, hs) views.  Returns
         ``ws.logits``: all rows, or only the last row when the workspace was built with ``lm_rows == 1``.
+        Batched decode (``ws.rows_are_sequences``): row b embeds ``tokens[b, tok_pos[b]]`` (``tokens[b, 0]`` without tok_pos)
+        at position ``pos[b]`` (int32[M]); ``caches[i]`` are the (M, n_groups, S, hs) caches of the M sequences.
         """
         M = ws.M
-        ops.embedding(self.transformer.wte.weight.data, tokens, tok_pos, M, ws.x)
-        nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, M)
+        if ws.rows_are_sequences:
+            ops.embedding_rows(self.transformer.wte.weight.data, tokens, tok_pos, ws.x)
+            nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, 1)  # each row splits as one sequence does
+        else:
+            ops.embedding(self.transformer.wte.weight.data, tokens, tok_pos, M, ws.x)
+            nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, M)
         for block, (kc, vc) in zip(self.transformer.h, caches):
             block.run_rows(ws, pos, S, kc, vc, rope, nsplit, rope_local)
         last = ws.x if ws.lm_rows == M else ws.x[M - 1:M]
@@ -252,8 +279,14 @@ class GPT(nn.Module):
         else:
             S = T
             pos = None
-        ws = self.workspace(T, idx.device)
         idx = idx.to(torch.int64).contiguous()
+        if (use_kv_cache and T == 1 and 2 <= B <= ops.GEMV_MAX_ROWS and ops.BATCHED_DECODE
+                and self.batched_decode_unsupported() is None):
+            # one batched pass: row b is sequence b at the shared position (the reference's one input_pos), in cache slice b
+            ws = self.workspace(B, idx.device, B, rows_are_sequences=True)
+            logits = self.run_rows(ws, idx, None, pos.expand(B).contiguous(), S, self.kv_caches, self.rope_cache)
+            return logits.view(B, 1, -1).clone()
+        ws = self.workspace(T, idx.device)
         out = torch.empty((B, T, self.config.padded_vocab_size), dtype=torch.bfloat16, device=idx.device)
         for b in range(B):
             if use_kv_cache:
@@ -358,6 +391,11 @@ class CausalSelfAttention(nn.Module):
         c = self.config
         _linear(self.attn, x, ws.qkv, norm=norm)
         prefix = self.adapter_prefix()
+        if ws.rows_are_sequences:  # batched decode: one row per sequence, every row in one launch
+            if prefix is not None:
+                raise ParrotHipError("the batched decode step has no adapter-prefix term: adapter models decode one sequence at a time")
+            return ops.attn_fused_decode_rows(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv,
+                                              c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
         if ws.M == 1 and not rope_local and c.q_per_kv <= ops.FUSED_ATTN_MAX_Q_PER_KV:
             if prefix is not None:  # LLaMA-Adapter layer (adapter.py): the gated prefix term inside the same launch
                 return ops.attn_fused_decode_adapter(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,

@@ -1,7 +1,8 @@
 """Tensor-level wrappers over the C ABI (``_hip.py``): shape checks, pointer extraction, dispatch per Linear class.
 
 Everything here enqueues HIP kernels on the current torch stream and returns immediately; nothing falls back to a
-torch implementation.  Activations are bf16 rows ``(M, features)`` of ONE sequence.
+torch implementation.  Activations are bf16 rows ``(M, features)`` of ONE sequence, except in the batched-decode entry points
+(``*_rows``): there row b is the one new token of sequence b.
 """
 import ctypes as C
 import os
@@ -390,6 +391,32 @@ def attn_fused_decode(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n
     return y
 
 
+# GPT.forward(idx (B, 1), ...) with 2 <= B <= GEMV_MAX_ROWS runs the B sequences as ONE batched pass when the model allows it
+# (model.GPT.batched_decode_unsupported); False: one pass per sequence (tests compare the two)
+BATCHED_DECODE = True
+
+
+def attn_fused_decode_rows(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_elem: int, pos: torch.Tensor,
+                           k_cache: torch.Tensor, v_cache: torch.Tensor, n_groups: int, q_per_kv: int, hs: int, S: int,
+                           nsplit: int, workspace: torch.Tensor, tickets: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Batched decode: row b of ``qkv`` is the new token of sequence b at position ``pos[b]``, with its own caches
+    ``k_cache[b]`` / ``v_cache[b]`` ((B, n_groups, S, hs)); attn_fused_decode for the B rows in one launch."""
+    _rows(qkv, "attn_fused_decode_rows"), _rows(y, "attn_fused_decode_rows")
+    B = qkv.shape[0]
+    if pos.dtype != torch.int32 or pos.numel() != B or not pos.is_contiguous():
+        raise ParrotHipError("attn_fused_decode_rows: pos must be a contiguous int32 vector of one position per row")
+    for c in (k_cache, v_cache):
+        if c.dtype != torch.bfloat16 or c.dim() != 4 or c.shape[0] < B or tuple(c.shape[1:]) != (n_groups, S, hs) or not c[0].is_contiguous():
+            raise ParrotHipError(f"attn_fused_decode_rows: caches must be bf16 (B, n_groups, S, hs), got {tuple(c.shape)}")
+    if k_cache.stride(0) != v_cache.stride(0) or y.shape[0] != B or tickets.dtype != torch.int32:
+        raise ParrotHipError("attn_fused_decode_rows: K / V caches with one batch stride, y (B, n_head * hs), int32 tickets expected")
+    check(_hip.load().parrot_attn_fused_decode_rows(ptr(qkv), qkv.stride(0), B, ptr(cos), ptr(sin), n_elem, ptr(pos), n_groups, q_per_kv,
+                                                    hs, S, nsplit, ptr(workspace), ptr(tickets), tickets.numel(), ptr(k_cache),
+                                                    ptr(v_cache), k_cache.stride(0), ptr(y), y.stride(0), ATTN_SOFTMAX_MODE, stream()),
+          "parrot_attn_fused_decode_rows")
+    return y
+
+
 class AdapterPrefix:
     """The LLaMA-Adapter prefix of one layer (lit_gpt/adapter.py:226-254): keys / values (n_groups, aT, hs) bf16 - no RoPE,
     GQA-native - and the per-head gate (n_head,) bf16 (``gating_factor``)."""
@@ -445,6 +472,53 @@ def embedding(wte: torch.Tensor, tokens: torch.Tensor, pos: Optional[torch.Tenso
     check(_hip.load().parrot_embedding(ptr(wte), wte.shape[1], ptr(tokens), ptr(pos), M, ptr(out), out.stride(0),
                                        stream()), "parrot_embedding")
     return out
+
+
+def embedding_rows(wte: torch.Tensor, tokens: torch.Tensor, pos: Optional[torch.Tensor], out: torch.Tensor) -> torch.Tensor:
+    """Batched decode: ``out[b] = wte[tokens[b, pos[b] if pos is not None else 0]]`` for the B rows of ``tokens`` (B, L)."""
+    _rows(out, "embedding_rows")
+    if wte.dtype != torch.bfloat16 or not wte.is_contiguous() or tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.stride(1) != 1:
+        raise ParrotHipError("embedding_rows: wte must be contiguous bf16 and tokens int64 rows (B, L)")
+    B = tokens.shape[0]
+    if out.shape[0] != B or (pos is not None and (pos.dtype != torch.int32 or pos.numel() != B)):
+        raise ParrotHipError("embedding_rows: out (B, d) and an int32 pos of B positions expected")
+    check(_hip.load().parrot_embedding_rows(ptr(wte), wte.shape[1], ptr(tokens), tokens.stride(0), ptr(pos), B, ptr(out), out.stride(0),
+                                            stream()), "parrot_embedding_rows")
+    return out
+
+
+def _sample_rows_args(what: str, logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, end: torch.Tensor) -> int:
+    B = logits.shape[0]
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ParrotHipError(f"{what}: logits must be bf16 rows (B, V)")
+    if tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.shape[0] != B or tokens.stride(1) != 1:
+        raise ParrotHipError(f"{what}: tokens must be int64 rows (B, L)")
+    for t, nm in ((pos, "pos"), (end, "end")):
+        if t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous():
+            raise ParrotHipError(f"{what}: {nm} must be a contiguous int32 vector of B = {B} entries")
+    return B
+
+
+def argmax_advance_rows(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, end: torch.Tensor, eos_id: int = -1) -> None:
+    """Batched greedy step: per row b, ``tokens[b, pos[b] + 1]`` = argmax(logits[b]), ``pos[b] += 1`` - unless the row is frozen
+    (next position at ``end[b]``, or its last token is ``eos_id``; -1: none)."""
+    B = _sample_rows_args("argmax_advance_rows", logits, tokens, pos, end)
+    check(_hip.load().parrot_argmax_advance_rows(ptr(logits), logits.shape[1], logits.stride(0), B, ptr(tokens), tokens.stride(0), ptr(pos),
+                                                 ptr(end), int(eos_id), stream()), "parrot_argmax_advance_rows")
+
+
+def topk_sample_rows(logits: torch.Tensor, temperature: float, top_k: Optional[int], noise: torch.Tensor, tokens: torch.Tensor,
+                     pos: torch.Tensor, end: torch.Tensor, eos_id: int = -1) -> None:
+    """Batched sampling step: topk_sample on row b of ``logits`` with row b of ``noise`` (B, V), frozen rows as in argmax_advance_rows."""
+    B = _sample_rows_args("topk_sample_rows", logits, tokens, pos, end)
+    V = logits.shape[1]
+    if noise.dtype != torch.bfloat16 or tuple(noise.shape) != (B, V) or not noise.is_contiguous():
+        raise ParrotHipError("topk_sample_rows: noise must be contiguous bf16 (B, V)")
+    if not temperature > 0:
+        raise ParrotHipError(f"topk_sample_rows: temperature must be positive (got {temperature})")
+    check(_hip.load().parrot_topk_sample_rows(ptr(logits), V, logits.stride(0), B, float(temperature), int(top_k) if top_k is not None else 0,
+                                              ptr(noise), ptr(tokens), tokens.stride(0), ptr(pos), ptr(end), int(eos_id), stream()),
+          "parrot_topk_sample_rows")
 
 
 def argmax_advance(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor) -> None:
