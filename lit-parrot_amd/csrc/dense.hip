@@ -1,7 +1,7 @@
 // Dense bf16 Linear for the decode step: y = epilogue(x @ W^T + b), W (N, K) row-major bf16.
 // Reference: torch.nn.Linear on the bf16-true path (lit_gpt/model.py:29,188,190,281-282,293-295).
 //
-// Memory-bound GEMV with the structure of the int4 kernel (w4.hip), which is where it was measured:
+// Memory-bound GEMV on the skeleton shared with the int4 kernel (gemv_common.h), which is where it was measured:
 //   * workgroup = nslabs x wps waves; wave (slab c, j) owns the chunks of slab c of K (16 B = 8 bf16 per lane and load,
 //     J loads per row, 64 lanes = 1 KiB contiguous each) of RU consecutive rows of row group j;
 //   * the activations - and the optional RMSNorm / LayerNorm of them - are prepared ONCE per workgroup through LDS
@@ -11,7 +11,7 @@
 //   * the grid is what is resident at once and every workgroup walks `iters` batches of rows;
 //   * fp32 accumulation through v_dot2c_f32_bf16, wave reduction (DPP), cross-slab reduction in LDS, fused epilogue
 //     whose bias / residual elements are requested at batch start.
-#include "parrot_common.h"
+#include "gemv_common.h"
 
 namespace parrot {
 
@@ -28,7 +28,7 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
     extern __shared__ __attribute__((aligned(16))) unsigned char dense_smem[];  // normalised activations [M][K] bf16 (norm only)
     __shared__ float red[2][MAXW][RU * M * NW];
     __shared__ float stat[16];
-    __builtin_amdgcn_s_setprio(3);  // prologue at raised priority, see w4.hip
+    __builtin_amdgcn_s_setprio(3);  // prologue at raised wave priority (gemv_common.h)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = nslabs * wps;
@@ -47,7 +47,6 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
         cidx[jj] = cok[jj] ? c : c1 - 1;
     }
     uint32_t xr[M][J][4];
-    constexpr int kMaxChunkIt = 4;  // K <= 4 * 8 * nthreads is checked on the host for the norm path
     uint4 cx[M][kMaxChunkIt], cw[kMaxChunkIt], cb[kMaxChunkIt];
     if (na.kind == 0) {
 #pragma unroll
@@ -154,21 +153,10 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
     }
 
     __builtin_amdgcn_s_setprio(0);
-    const bf16_t* res_p = residual != nullptr ? residual : reinterpret_cast<const bf16_t*>(W);
-    const bf16_t* bias_p = bias != nullptr ? bias : reinterpret_cast<const bf16_t*>(W);
-    const int e_m = threadIdx.x % M, e_ur = threadIdx.x / M;
+    const GemvEpilogue<M, DUAL, AD> ep(W, bias, residual, ldr);
     for (int t = 0; t < iters; ++t) {
         float(*rd)[RU * M * NW] = red[t & 1];
-        const int e_col = min(((int)blockIdx.x + t * (int)gridDim.x) * R + e_ur, N - 1);
-        const bf16_t e_res = res_p[residual != nullptr ? (int64_t)e_m * ldr + e_col : 0];
-        const bf16_t e_bias = bias_p[bias != nullptr ? e_col : 0];
-        float e_as = 1.f, e_ab = 0.f, e_as2 = 1.f, e_ab2 = 0.f;
-        if constexpr (AD) {
-            if (ad.scale != nullptr) e_as = bf2f(ad.scale[e_col]);
-            if (ad.bias != nullptr) e_ab = bf2f(ad.bias[e_col]);
-            if (DUAL && ad.scale2 != nullptr) e_as2 = bf2f(ad.scale2[e_col]);
-            if (DUAL && ad.bias2 != nullptr) e_ab2 = bf2f(ad.bias2[e_col]);
-        }
+        const GemvEpiOperands eo = ep.request(N, R, t, ad);
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             if (u + PRIME < RU) {
@@ -177,11 +165,7 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
                 DENSE_ISSUE_ROW(t + 1, u + PRIME - RU)
             }
             asm volatile("" ::: "memory");
-            if (RU >= 4) {  // waves that are behind run at higher priority than waves that are ahead
-                if (u == 0) __builtin_amdgcn_s_setprio(2);
-                if (u == RU / 4) __builtin_amdgcn_s_setprio(1);
-                if (u == RU / 2) __builtin_amdgcn_s_setprio(0);
-            }
+            gemv_prio_ladder<RU, 2>(u);
             float part[NW][M];
 #pragma unroll
             for (int q = 0; q < NW; ++q)
@@ -205,23 +189,7 @@ bf16_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, cons
                     if (lane == 63) rd[wave][(u * M + m) * NW + q] = part[q][m];
         }
         __syncthreads();
-        if ((int)threadIdx.x < R * M) {
-            const int m = threadIdx.x % M, ur = threadIdx.x / M;
-            const int jj = ur / RU, u = ur % RU;
-            const int col = ((int)blockIdx.x + t * (int)gridDim.x) * R + ur;
-            if (col < N) {
-                float a0 = 0.f, a1 = 0.f;
-                for (int c = 0; c < nslabs; ++c) {
-                    a0 += rd[c * wps + jj][(u * M + m) * NW];
-                    if (DUAL) a1 += rd[c * wps + jj][(u * M + m) * NW + 1];
-                }
-                if constexpr (AD)
-                    out[(int64_t)m * ldo + col] = apply_epilogue_adapter_vals(epi, a0, a1, bias != nullptr, bf2f(e_bias), bf2f(e_res),
-                                                                              e_as, e_ab, e_as2, e_ab2);
-                else
-                    out[(int64_t)m * ldo + col] = apply_epilogue_vals(epi, a0, a1, bias != nullptr, bf2f(e_bias), bf2f(e_res));
-            }
-        }
+        if ((int)threadIdx.x < R * M) ep.template sum_store<RU>(rd, nslabs, wps, N, R, t, epi, eo, out, ldo);
     }
 #undef DENSE_ISSUE_ROW
 #undef DENSE_ROW0
@@ -240,23 +208,17 @@ static int bf16_gemv_launch_jw(const void* W, const void* W2, const void* x, int
     if (na.kind != 0)  // the cooperative norm covers 4 x 8 x nthreads elements of K
         while (wps * nslabs < MAXW && (K >> 3) > 4 * 64 * nslabs * wps) ++wps;
     const int nthreads = 64 * nslabs * wps;
-    size_t lds = 0;
-    if (na.kind != 0) {
-        PARROT_UNSUPPORTED((K >> 3) <= 4 * nthreads, "bf16_gemv: fused norm needs K <= %d with this workgroup shape", 32 * nthreads);
-        lds = (size_t)M * K * 2;
-        PARROT_UNSUPPORTED(lds <= 64 * 1024, "bf16_gemv: fused norm needs %zu B of LDS", lds);
-    }
-    const int R = wps * ru;
-    const int batches = (N + R - 1) / R;
+    size_t lds;
+    const int rc = gemv_fused_norm_lds("bf16_gemv", na, M, K, nthreads, &lds);
+    if (rc != PARROT_OK) return rc;
     const int per_simd = J <= 5 ? 4 : (J <= 6 ? 3 : 2);  // waves per SIMD the build's VGPR count allows (<= 128 / 170 / 256)
-    const int resident = 256 * (4 * per_simd / (nslabs * wps) > 0 ? 4 * per_simd / (nslabs * wps) : 1);
-    const int iters = (batches + resident - 1) / resident;
-    const dim3 grid((batches + iters - 1) / iters), block(nthreads);
+    const GemvGrid g = gemv_grid(N, wps * ru, gemv_resident(4 * per_simd, nslabs * wps));
+    const dim3 grid(g.grid), block(nthreads);
     const AdapterArgs adv = ad ? *ad : AdapterArgs{nullptr, nullptr, nullptr, nullptr};
 #define PARROT_DENSE_GO(KID, DUALV, RUV, ADV)                                                                             \
     return launch(KID, bf16_gemv_kernel<M, DUALV, J, RUV, MAXW, ADV>, grid, block, lds, st, (const uint4*)W, (const uint4*)W2, \
                   (const bf16_t*)x, ldx, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, N, K, wps,      \
-                  nslabs, epi, iters, na, adv)
+                  nslabs, epi, g.iters, na, adv)
     if (dual) {
         if (ad) PARROT_DENSE_GO(K_BF16_GEMV_DUAL, true, RUD, true);
         PARROT_DENSE_GO(K_BF16_GEMV_DUAL, true, RUD, false);
@@ -313,20 +275,9 @@ static int bf16_gemv_entry(const void* W, const void* W2, const void* x, int ldx
     rc = make_norm_args(norm, K, &na);
     if (rc != PARROT_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bf16_t* xb = (const bf16_t*)x;
-    const bf16_t* rb = (const bf16_t*)residual;
-    bf16_t* ob = (bf16_t*)out;
-    for (int m0 = 0; m0 < M; m0 += 2) {
-        const void* xm = xb + (int64_t)m0 * ldx;
-        const void* rm = rb ? rb + (int64_t)m0 * ldr : nullptr;
-        void* om = ob + (int64_t)m0 * ldo;
-        if (M - m0 >= 2)
-            rc = bf16_gemv_launch<2>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, ad, st);
-        else
-            rc = bf16_gemv_launch<1>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, ad, st);
-        if (rc != PARROT_OK) return rc;
-    }
-    return PARROT_OK;
+    return gemv_for_row_chunks<2>(x, ldx, M, residual, ldr, out, ldo, [&](auto rows, const void* xm, const void* rm, void* om) {
+        return bf16_gemv_launch<decltype(rows)::value>(W, W2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, ad, st);
+    });
 }
 
 // adapter-v2 vectors of the GEMV / element-wise entry points: every vector given is 2-byte aligned device memory; the partner's

@@ -15,7 +15,7 @@
 // The +128 bias is removed with the per-lane sum of x: s * (sum x*(128+q) - (128+z) * sum x).
 #include <stdlib.h>
 
-#include "parrot_common.h"
+#include "gemv_common.h"
 #include "w4_plan.h"
 
 namespace parrot {
@@ -134,11 +134,7 @@ w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const 
     __shared__ float stat[16];
 
     w4_stamp(dbg, 0);
-    // The prologue (activations, fused norm) runs at raised wave priority: the SIMDs arbitrate oldest-first, so without it
-    // the 3rd / 4th workgroup of a CU gets its norm instructions in only when the older workgroups' dot loops stall
-    // (measured: norm ready at +3.4 us in the first workgroup of a CU, +7.5 .. +10 us in the last), and the launch ends
-    // when the slowest workgroup does.  Priority drops back before the dot loop.
-    __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);  // prologue at raised wave priority (gemv_common.h); it drops back before the dot loop
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = plan.nslabs * wps;
@@ -156,7 +152,6 @@ w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const 
     uint32_t xr[M][16];
     const int nthreads = nwaves * 64;
     const int chunks = K >> 3;  // 16-byte units of a row of x
-    constexpr int kMaxChunkIt = 4;  // K <= 4 * 8 * nthreads is checked on the host for the norm path
     uint4 cx[M][kMaxChunkIt], cw[kMaxChunkIt], cb[kMaxChunkIt];
     if (na.kind == 0) {
 #pragma unroll
@@ -309,19 +304,12 @@ w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const 
     w4_stamp(dbg, 1);
     __builtin_amdgcn_s_setprio(0);
 
-    // bias / residual elements of the epilogue threads: requested at the START of a batch (every thread, clamped, always:
-    // a load behind a condition would cost the compiler its static vmcnt bookkeeping), so that the kernel's tail does not
-    // end with "load residual -> wait a full memory latency -> add -> store"
-    const bf16_t* res_p = residual != nullptr ? residual : reinterpret_cast<const bf16_t*>(W);
-    const bf16_t* bias_p = bias != nullptr ? bias : reinterpret_cast<const bf16_t*>(W);
-    const int e_m = threadIdx.x % M, e_ur = threadIdx.x / M;
+    const GemvEpilogue<M, DUAL, false> ep(W, bias, residual, ldr);
     constexpr bool kSum8 = (M == 1 && RU == 8);  // eight row sums in one packed reduction (wave_sum8)
     float lanep[NW][8];
     for (int t = 0; t < iters; ++t) {
         float(*rd)[RU * M * NW] = red[t & 1];
-        const int e_col = min(((int)blockIdx.x + t * (int)gridDim.x) * R + e_ur, N - 1);
-        const bf16_t e_res = res_p[residual != nullptr ? (int64_t)e_m * ldr + e_col : 0];
-        const bf16_t e_bias = bias_p[bias != nullptr ? e_col : 0];
+        const GemvEpiOperands eo = ep.request(N, R, t);
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             // request row u + PRIME: of this batch, or - across the batch boundary - of the next one
@@ -331,14 +319,7 @@ w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const 
                 W4_ISSUE_ROW(t + 1, u + PRIME - RU)
             }
             asm volatile("" ::: "memory");
-            // waves that are behind run at higher priority than waves that are ahead (the SIMD's default is oldest first,
-            // which lets the first workgroup of a CU finish early and leaves its share of the memory queue idle)
-            if (RU >= 4) {
-                if (u == 0) __builtin_amdgcn_s_setprio(3);
-                if (u == RU / 4) __builtin_amdgcn_s_setprio(2);
-                if (u == RU / 2) __builtin_amdgcn_s_setprio(1);
-                if (u == (3 * RU) / 4) __builtin_amdgcn_s_setprio(0);
-            }
+            gemv_prio_ladder<RU, 3>(u);
             // consume row u (its registers are re-filled PRIME steps later at the earliest ... by row u + PRIME - RU of the
             // next batch, which is only requested after this use)
             float part[NW][M];
@@ -386,20 +367,7 @@ w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const 
         if (t == 0) w4_stamp(dbg, 2);
         __syncthreads();
         if (t == 0) w4_stamp(dbg, 3);
-        // epilogue: one thread per (row of the batch, m); sums the slabs in a fixed order
-        if ((int)threadIdx.x < R * M) {
-            const int m = threadIdx.x % M, ur = threadIdx.x / M;
-            const int jj = ur / RU, u = ur % RU;
-            const int col = ((int)blockIdx.x + t * (int)gridDim.x) * R + ur;
-            if (col < N) {
-                float a0 = 0.f, a1 = 0.f;
-                for (int c = 0; c < plan.nslabs; ++c) {
-                    a0 += rd[c * wps + jj][(u * M + m) * NW];
-                    if (DUAL) a1 += rd[c * wps + jj][(u * M + m) * NW + 1];
-                }
-                out[(int64_t)m * ldo + col] = apply_epilogue_vals(epi, a0, a1, bias != nullptr, bf2f(e_bias), bf2f(e_res));
-            }
-        }
+        if ((int)threadIdx.x < R * M) ep.template sum_store<RU>(rd, plan.nslabs, wps, N, R, t, epi, eo, out, ldo);
     }
 #undef W4_ISSUE_ROW
 #undef W4_ROW0
@@ -436,24 +404,18 @@ static int w4_gemv_launch_v(const void* packed, const void* packed2, const void*
                             const void* residual, int ldr, void* out, int ldo, int N, int K, int epi, const NormArgs& na,
                             const W4Plan& plan, hipStream_t st, const void* code) {
     const int wps = pick_wps(N, RU, plan.nslabs, MAXW, na.kind != 0);
-    const int R = wps * RU;
     const int nthreads = 64 * plan.nslabs * wps;
-    size_t lds = 0;
-    if (na.kind != 0) {
-        PARROT_UNSUPPORTED((K >> 3) <= 4 * nthreads, "w4_gemv: fused norm needs K <= %d with this workgroup shape", 32 * nthreads);
-        lds = (size_t)M * K * 2;
-        PARROT_UNSUPPORTED(lds <= 64 * 1024, "w4_gemv: fused norm needs %zu B of LDS", lds);
-    }
-    // grid = what is resident at once (4 waves per SIMD with either build), every workgroup walks `iters` batches of rows
-    const int batches = (N + R - 1) / R;
-    int resident = 256 * (16 / (plan.nslabs * wps) > 0 ? 16 / (plan.nslabs * wps) : 1);
+    size_t lds;
+    const int rc = gemv_fused_norm_lds("w4_gemv", na, M, K, nthreads, &lds);
+    if (rc != PARROT_OK) return rc;
+    int resident = gemv_resident(16, plan.nslabs * wps);  // 4 waves per SIMD with either build
     if (g_resident_override > 0) resident = g_resident_override;
-    const int iters = (batches + resident - 1) / resident;
-    const dim3 grid((batches + iters - 1) / iters), block(nthreads);
+    const GemvGrid g = gemv_grid(N, wps * RU, resident);
+    const dim3 grid(g.grid), block(nthreads);
     return launch(CB ? (DUAL ? K_W4C_GEMV_DUAL : K_W4C_GEMV) : (DUAL ? K_W4_GEMV_DUAL : K_W4_GEMV),
                   w4_gemv_kernel<M, DUAL, RU, MAXW, CB>, grid, block, lds, st,
                   (const uint4*)packed, (const uint4*)packed2, (const bf16_t*)x, ldx, (const bf16_t*)bias,
-                  (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, N, K, wps, epi, iters, na, plan, g_w4_dbg_host,
+                  (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, N, K, wps, epi, g.iters, na, plan, g_w4_dbg_host,
                   (const uint32_t*)code);
 }
 
@@ -493,23 +455,9 @@ static int w4_gemv_entry(const char* who, const void* packed, const void* packed
     rc = make_norm_args(norm, K, &na);
     if (rc != PARROT_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bf16_t* xb = (const bf16_t*)x;
-    const bf16_t* rb = (const bf16_t*)residual;
-    bf16_t* ob = (bf16_t*)out;
-    for (int m0 = 0; m0 < M; m0 += 4) {
-        const int mm = (M - m0 < 4) ? M - m0 : 4;
-        const void* xm = xb + (int64_t)m0 * ldx;
-        const void* rm = rb ? rb + (int64_t)m0 * ldr : nullptr;
-        void* om = ob + (int64_t)m0 * ldo;
-        switch (mm) {
-            case 1: rc = w4_gemv_launch<1, CB>(packed, packed2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, plan, st, code); break;
-            case 2: rc = w4_gemv_launch<2, CB>(packed, packed2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, plan, st, code); break;
-            case 3: rc = w4_gemv_launch<3, CB>(packed, packed2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, plan, st, code); break;
-            default: rc = w4_gemv_launch<4, CB>(packed, packed2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, plan, st, code); break;
-        }
-        if (rc != PARROT_OK) return rc;
-    }
-    return PARROT_OK;
+    return gemv_for_row_chunks<4>(x, ldx, M, residual, ldr, out, ldo, [&](auto rows, const void* xm, const void* rm, void* om) {
+        return w4_gemv_launch<decltype(rows)::value, CB>(packed, packed2, xm, ldx, bias, rm, ldr, om, ldo, N, K, epilogue, na, plan, st, code);
+    });
 }
 
 // Codebook weights -> dense bf16 (N, K): w = bf16(code[q] * absmax), the rounding bitsandbytes' dequantize_4bit applies before

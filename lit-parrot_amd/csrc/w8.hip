@@ -12,7 +12,7 @@
 
 #include <stdlib.h>
 
-#include "parrot_common.h"
+#include "gemv_common.h"
 
 namespace parrot {
 
@@ -334,7 +334,7 @@ static int w8_launch(const void* CB, const void* CB2, const void* SCB, const voi
 }
 
 // ------------------------------------------------------------------------------------------ fused single-token Linear
-// Decode step (one row): activation quantiser + GEMV in ONE launch, on the structure of the int4 kernel (w4.hip):
+// Decode step (one row): activation quantiser + GEMV in ONE launch, on the skeleton of gemv_common.h:
 // workgroup = nslabs x wps waves; the prologue (optional norm -> fp16 cast -> outlier split -> row absmax -> int8) is
 // computed once per workgroup into LDS ([K] int8, [K] fp16 outlier values, a compact list of the first kW8Cap outlier
 // columns in a deterministic thread-major order); weight rows go through a rolling window; resident-size grid walking
@@ -355,7 +355,7 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
     __shared__ int scan[16];
     __shared__ int olist[kW8Cap];
     __shared__ int s_total;
-    __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);  // prologue at raised wave priority (gemv_common.h)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = nslabs * wps;
@@ -377,10 +377,9 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
     }
     // ---- activation row: thread t owns the 8-element chunks t, t + nthreads, ... (rounds past the row are skipped)
     const int chunks8 = K >> 3;
-    constexpr int kIt = 4;  // K <= 4 * 8 * nthreads (host)
-    uint4 cx[kIt], cw[kIt], cb[kIt];
+    uint4 cx[kMaxChunkIt], cw[kMaxChunkIt], cb[kMaxChunkIt];
 #pragma unroll
-    for (int it = 0; it < kIt; ++it) {
+    for (int it = 0; it < kMaxChunkIt; ++it) {
         cx[it] = cw[it] = cb[it] = make_uint4(0, 0, 0, 0);
         if (it * nthreads < chunks8) {
             const int c = threadIdx.x + it * nthreads;
@@ -411,7 +410,7 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
     if (na.kind != 0) {
         float s1 = 0.f;
 #pragma unroll
-        for (int it = 0; it < kIt; ++it) {
+        for (int it = 0; it < kMaxChunkIt; ++it) {
             if (it * nthreads < chunks8) {
                 const uint32_t dw[4] = {cx[it].x, cx[it].y, cx[it].z, cx[it].w};
                 float t = 0.f;
@@ -422,10 +421,10 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
         }
         s1 = block_sum_waves(s1, stat, nwaves);
         if (na.kind == 2) {
-            mean = s1 / (float)K;
+            mean = s1 / (float)K;  // K == na.d (make_norm_args sets d = K)
             float s2 = 0.f;
 #pragma unroll
-            for (int it = 0; it < kIt; ++it) {
+            for (int it = 0; it < kMaxChunkIt; ++it) {
                 if (threadIdx.x + it * nthreads < chunks8) {
                     const uint32_t dw[4] = {cx[it].x, cx[it].y, cx[it].z, cx[it].w};
 #pragma unroll
@@ -437,11 +436,11 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
             r = norm_scale(na, s1);
         }
     }
-    float a[kIt][8];
+    float a[kMaxChunkIt][8];
     float mx = 0.f;
     int local = 0;
 #pragma unroll
-    for (int it = 0; it < kIt; ++it) {
+    for (int it = 0; it < kMaxChunkIt; ++it) {
         const bool ok = threadIdx.x + it * nthreads < chunks8;
         const uint32_t raw[4] = {cx[it].x, cx[it].y, cx[it].z, cx[it].w};
         uint32_t nrm[4] = {raw[0], raw[1], raw[2], raw[3]};
@@ -483,7 +482,7 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
     const float inv = mx > 0.f ? __fdiv_rn(127.0f, mx) : 0.f;
     int slot = base + incl - local;
 #pragma unroll
-    for (int it = 0; it < kIt; ++it) {
+    for (int it = 0; it < kMaxChunkIt; ++it) {
         const int c = threadIdx.x + it * nthreads;
         if (c < chunks8) {
             uint32_t q8[2] = {0, 0};
@@ -535,12 +534,7 @@ w8_fused_kernel(const uint4* __restrict__ CB, const uint4* __restrict__ CB2, con
                 W8_ISSUE_ROW(t + 1, u + PRIME - RU)
             }
             asm volatile("" ::: "memory");
-            if (RU >= 4) {
-                if (u == 0) __builtin_amdgcn_s_setprio(3);
-                if (u == RU / 4) __builtin_amdgcn_s_setprio(2);
-                if (u == RU / 2) __builtin_amdgcn_s_setprio(1);
-                if (u == (3 * RU) / 4) __builtin_amdgcn_s_setprio(0);
-            }
+            gemv_prio_ladder<RU, 3>(u);
             int part[NW];
 #pragma unroll
             for (int q = 0; q < NW; ++q) {
@@ -617,19 +611,16 @@ static int w8_fused_launch(const void* CB, const void* CB2, const void* SCB, con
     PARROT_UNSUPPORTED((K >> 3) <= 4 * nthreads, "w8_gemv_fused: K=%d does not fit the workgroup's prologue", K);
     const size_t lds = (size_t)K * 3;
     PARROT_UNSUPPORTED(lds <= 56 * 1024, "w8_gemv_fused: K=%d needs %zu B of LDS", K, lds);
-    const int R = wps * ru;
-    const int batches = (N + R - 1) / R;
     const int per_simd = (J <= 2 && !dual) ? 3 : 2;  // waves per SIMD at this build's VGPR count (135 .. 201)
-    const int resident = 256 * (4 * per_simd / (nslabs * wps) > 0 ? 4 * per_simd / (nslabs * wps) : 1);
-    const int iters = (batches + resident - 1) / resident;
-    const dim3 grid((batches + iters - 1) / iters), block(nthreads);
+    const GemvGrid g = gemv_grid(N, wps * ru, gemv_resident(4 * per_simd, nslabs * wps));
+    const dim3 grid(g.grid), block(nthreads);
     if (dual)
         return launch(K_W8_GEMV, w8_fused_kernel<true, J, RUD, MAXW>, grid, block, lds, st, (const uint4*)CB, (const uint4*)CB2,
                       (const float*)SCB, (const float*)SCB2, (const bf16_t*)x, threshold, (const bf16_t*)bias,
-                      (const bf16_t*)residual, (bf16_t*)out, N, K, wps, nslabs, epi, iters, na);
+                      (const bf16_t*)residual, (bf16_t*)out, N, K, wps, nslabs, epi, g.iters, na);
     return launch(K_W8_GEMV, w8_fused_kernel<false, J, RU, MAXW>, grid, block, lds, st, (const uint4*)CB, (const uint4*)CB2,
                   (const float*)SCB, (const float*)SCB2, (const bf16_t*)x, threshold, (const bf16_t*)bias,
-                  (const bf16_t*)residual, (bf16_t*)out, N, K, wps, nslabs, epi, iters, na);
+                  (const bf16_t*)residual, (bf16_t*)out, N, K, wps, nslabs, epi, g.iters, na);
 }
 
 // ------------------------------------------------------------------------------------------ int8 GEMM (prefill)
