@@ -236,6 +236,16 @@ int parrot_attn_fused_decode_rows(const void* qkv, int ldqkv, int B, const void*
                                   const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
                                   void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
                                   int softmax_mode, void* stream);
+/* Speculative decode: the same step for M CONSECUTIVE tokens of ONE sequence (1 <= M <= 8) in one launch.  Row m: qkv + m*ldqkv, the
+ * token at position pos[0] + m (pos: int32[1]); it attends to slots 0 .. pos[0] + m of the one cache and writes y + m*ldy.  Nothing
+ * is appended here: run parrot_qkv_rope_kvappend over the same M rows FIRST (its cache rows are bit-equal to the fused kernel's),
+ * so that no workgroup reads a slot another workgroup of this launch writes.  The caller rules out a ring wrap inside the call
+ * (pos[0] + M <= S) and positions past the RoPE tables.  workspace / tickets as parrot_attn_fused_decode_rows (row m owns slice m).
+ * Row m's y is bit for bit what the m-th of M consecutive parrot_attn_fused_decode calls with the same nsplit writes.          */
+int parrot_attn_fused_decode_seq(const void* qkv, int ldqkv, int M, const void* rope_cos, const void* rope_sin, int n_elem,
+                                 const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                 void* tickets, int n_tickets, void* k_cache, void* v_cache, void* y, int ldy, int softmax_mode,
+                                 void* stream);
 /* LLaMA-Adapter prefix attention (lit_gpt/adapter.py:226-254) in the same launch: ak / av [n_groups][aT][hs] bf16 (the
  * prefix keys / values: no RoPE), gate [n_head] bf16 (gating_factor), 1 <= aT <= 64.  The workgroup that writes y attends
  * every roped query head to all aT prefix keys (own softmax, scale 1/sqrt(hs)) and writes
@@ -294,6 +304,27 @@ int parrot_argmax_advance_rows(const void* logits, int V, int ldl, int B, int64_
                                int eos_id, void* stream);
 int parrot_topk_sample_rows(const void* logits, int V, int ldl, int B, float temperature, int top_k, const void* noise_exp1,
                             int64_t* tokens, int ldt, int32_t* pos, const int32_t* end, int eos_id, void* stream);
+
+/* ---- prompt-lookup speculative decoding (greedy) -----------------------------------------------------------
+ * state: int32[8] beside tokens / pos: [0] drafts the last parrot_ngram_draft copied from an earlier occurrence (0: no match),
+ * [1] accepted drafts and [2] advancing steps summed by parrot_verify_advance, [3] *pos and [4] tokens[*pos] as the last
+ * parrot_ngram_draft saw them (one host read per step), [5..7] reserved.
+ *
+ * parrot_ngram_draft: tokens[0 .. *pos] are known (tokens: int64[L]).  For n = ngram_max down to ngram_min (1 <= n <= 16; an n
+ * with *pos - n + 1 < 0 is skipped) find the LARGEST j with j + n <= *pos and tokens[j .. j+n-1] == tokens[*pos-n+1 .. *pos]; on
+ * the first n with a match, draft i = tokens[j + n + i] for every i with j + n + i <= *pos.  Every remaining draft, and all
+ * draft_len (1 .. 7) of them without a match, is tokens[*pos].  The drafts are written to tokens[*pos+1 .. *pos+draft_len]
+ * (slots >= L are dropped).  One workgroup, one max-reduction: the result does not depend on scheduling.                      */
+int parrot_ngram_draft(int64_t* tokens, int L, const int32_t* pos, int draft_len, int ngram_max, int ngram_min, int32_t* state,
+                       void* stream);
+/* Greedy verification of M = draft_len + 1 rows of logits [M][ldl] (row m: position *pos + m): a_m = arg-max of row m exactly as
+ * parrot_argmax_advance computes it (lowest index on ties); c = the number of leading m < M-1 with a_m == tokens[*pos+1+m], cut
+ * so that no token is written at or past min(*end, L) and, with eos_id >= 0, at the first a_m == eos_id.  tokens[*pos+1+c] = a_c,
+ * *pos += c + 1, state[1] += c, state[2] += 1, row_pos[m] (int32[M], may be NULL) = the new *pos + m, the positions of the next
+ * step's rows.  Frozen (as parrot_argmax_advance_rows: *pos + 1 >= min(*end, L), or tokens[*pos] == eos_id): nothing is written
+ * but row_pos.  With all drafts right this is M consecutive parrot_argmax_advance calls.                                      */
+int parrot_verify_advance(const void* logits, int V, int ldl, int M, int64_t* tokens, int L, int32_t* pos, const int32_t* end,
+                          int eos_id, int32_t* state, int32_t* row_pos, void* stream);
 
 /* ---- stream engine: ONE launch per decode token ------------------------------------------------------------
  * The whole token (generate/base.py:131-153 for one iteration: embedding, every Block of lit_gpt/model.py:158-180,

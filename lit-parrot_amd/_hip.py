@@ -99,6 +99,7 @@ SIGNATURES = {
     "parrot_attn_decode": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_fused_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "parrot_attn_fused_decode_rows": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _i, _vp]),
+    "parrot_attn_fused_decode_seq": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_fused_decode_adapter": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_adapter_prefix": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "parrot_attn_prefill_scratch_elems": (_i64, [_i, _i, _i]),
@@ -121,6 +122,8 @@ SIGNATURES = {
     "parrot_topk_sample": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "parrot_argmax_advance_rows": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "parrot_topk_sample_rows": (_i, [_vp, _i, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "parrot_ngram_draft": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "parrot_verify_advance": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -512,7 +512,11 @@ struct AttnRowsArgs {
 
 // AD: the LLaMA-Adapter prefix term is added by the workgroup that writes y (AD = false is the plain kernel)
 // ROWS: the batched-decode instantiation; with ROWS = false `rows` is never read and the kernel is the one-row kernel
-template <int HS, int HQ, int WAVES, bool PM = false, bool AD = false, bool ROWS = false>  // PM: "softmax_mode 1", see attn_decode_kernel
+// SEQ (with ROWS): the rows are CONSECUTIVE tokens of ONE sequence (parrot_attn_fused_decode_seq): row b sits at position
+// pos[0] + b and attends to slots 0 .. pos[0] + b of the one shared cache (kv_bstride 0).  The K/V rows of all the rows were
+// appended by parrot_qkv_rope_kvappend in the launch before, so this instantiation appends nothing and no workgroup reads a
+// slot that another workgroup of the same launch writes; a row's own K/V still come from its registers.
+template <int HS, int HQ, int WAVES, bool PM = false, bool AD = false, bool ROWS = false, bool SEQ = false>  // PM: "softmax_mode 1", see attn_decode_kernel
 __global__ void __launch_bounds__(WAVES * 64)
 attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restrict__ rope_cos,
                          const __half* __restrict__ rope_sin, int n_elem, const int32_t* __restrict__ pos_ptr,
@@ -530,13 +534,17 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
 
     const int n_head = n_groups * q_per_kv;
     int chunk = blockIdx.z;  // chunk of the group's query heads
+    int seq_row = 0;         // SEQ: this row's offset from pos[0]
     unsigned int* ticket;
     if constexpr (ROWS) {
         const int nchunk = (q_per_kv + HQ - 1) / HQ;
         const int b = blockIdx.z / nchunk;
         chunk = blockIdx.z - b * nchunk;
         qkv += (int64_t)b * rows.ldqkv;
-        pos_ptr += b;
+        if constexpr (SEQ)
+            seq_row = b;
+        else
+            pos_ptr += b;
         k_cache += b * rows.kv_bstride;
         v_cache += b * rows.kv_bstride;
         ws += (int64_t)b * n_head * nsplit * (HS + 2);
@@ -549,7 +557,7 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     const int h0 = chunk * HQ;  // this workgroup's chunk of the group's query heads (GQA: chunks run in parallel)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, dl = lane % LPR;
-    const int pos = pos_ptr[0];
+    const int pos = SEQ ? pos_ptr[0] + seq_row : pos_ptr[0];
     const int n_valid = min(pos + 1, S);
     const int slot_new = pos % S;
     const int per = (S + nsplit - 1) / nsplit;
@@ -605,8 +613,8 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     }
     __syncthreads();
     attn_stamp(dbg, 1);
-    // ---- KV append by the workgroup that owns the new slot
-    if (chunk == 0 && slot_new >= s_begin && slot_new < s_begin + per && threadIdx.x < 2 * LPR) {
+    // ---- KV append by the workgroup that owns the new slot (SEQ: appended by the launch before)
+    if (!SEQ && chunk == 0 && slot_new >= s_begin && slot_new < s_begin + per && threadIdx.x < 2 * LPR) {
         const int which = threadIdx.x / LPR, c = threadIdx.x % LPR;
         bf16_t* dst = (which ? v_cache : k_cache) + ((int64_t)g * S + slot_new) * HS;
         reinterpret_cast<uint4*>(dst)[c] = reinterpret_cast<const uint4*>(sh_kv[which])[c];
@@ -804,8 +812,8 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     }
 }
 
-// B > 0 (ROWS): B sequences of one row each, strides in `rows`
-template <int HS, bool AD = false, bool ROWS = false>
+// B > 0 (ROWS): B sequences of one row each, strides in `rows`; SEQ: B consecutive rows of one sequence
+template <int HS, bool AD = false, bool ROWS = false, bool SEQ = false>
 static int attn_fused_launch(const void* qkv, const void* cosp, const void* sinp, int n_elem, const int32_t* pos,
                              void* k_cache, void* v_cache, int n_groups, int q_per_kv, int S, int nsplit, void* ws,
                              void* tickets, void* y, int softmax_mode, hipStream_t st, AdapterAttnArgs aa = {},
@@ -815,14 +823,14 @@ static int attn_fused_launch(const void* qkv, const void* cosp, const void* sinp
     const int per = (S + nsplit - 1) / nsplit;
     const bool wide = per > 2 * kAttnWaves * (64 / (HS / 8));
     const dim3 grid(n_groups, nsplit, B * ((q_per_kv + hq - 1) / hq)), block((wide ? 16 : kAttnWaves) * 64);
-    const int kid = ROWS ? K_ATTN_FUSED_ROWS : K_ATTN_FUSED;
+    const int kid = SEQ ? K_ATTN_FUSED_SEQ : (ROWS ? K_ATTN_FUSED_ROWS : K_ATTN_FUSED);
 #define PARROT_FUSED_GO(HQV, WV)                                                                                            \
     do {                                                                                                                    \
         if (softmax_mode == 1)                                                                                              \
-            return launch(kid, attn_fused_decode_kernel<HS, HQV, 16, true, AD, ROWS>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
+            return launch(kid, attn_fused_decode_kernel<HS, HQV, 16, true, AD, ROWS, SEQ>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
                           (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups, \
                           q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa, rows);   \
-        return launch(kid, attn_fused_decode_kernel<HS, HQV, WV, false, AD, ROWS>, grid, block, 0, st, (const bf16_t*)qkv, \
+        return launch(kid, attn_fused_decode_kernel<HS, HQV, WV, false, AD, ROWS, SEQ>, grid, block, 0, st, (const bf16_t*)qkv, \
                       (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups,   \
                       q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa, rows);       \
     } while (0)
@@ -947,40 +955,63 @@ int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* 
                             v_cache, y, softmax_mode, nullptr, stream);
 }
 
+}  // extern "C"
+
+// the batched entry point and, with SEQ, the consecutive-rows one (`who` names the caller in the messages)
+template <bool SEQ>
+static int attn_fused_rows_entry(const char* who, const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                 const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                 void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
+                                 int softmax_mode, void* stream) {
+    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "%s: B=%d (1 .. %d)", who, B, kMaxDecodeRows);
+    {
+        const int rc = check_softmax_mode(who, softmax_mode, S, nsplit);
+        if (rc != PARROT_OK) return rc;
+    }
+    PARROT_REQUIRE(qkv && pos && k_cache && v_cache && y, "%s: null pointer", who);
+    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1, "%s: bad shape", who);
+    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "%s: at most %d query heads per group (got %d)", who, kFusedMaxQ, q_per_kv);
+    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
+    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "%s: bad n_elem=%d", who, n_elem);
+    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "%s: rope tables missing", who);
+    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "%s: nsplit out of range", who);
+    const int n_head = n_groups * q_per_kv;
+    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "%s: workspace and tickets required when nsplit > 1", who);
+    PARROT_REQUIRE(!tickets || n_tickets >= B * n_head, "%s: %d tickets, B * n_head = %d needed", who, n_tickets, B * n_head);
+    PARROT_REQUIRE(ldqkv >= n_groups * (q_per_kv + 2) * hs && ldqkv % 8 == 0, "%s: ldqkv=%d too small or not a multiple of 8", who, ldqkv);
+    PARROT_REQUIRE(ldy >= n_head * hs, "%s: ldy=%d too small", who, ldy);
+    PARROT_REQUIRE(SEQ || (kv_bstride >= (int64_t)n_groups * S * hs && kv_bstride % 8 == 0),
+                   "%s: kv_bstride=%lld below n_groups * S * hs or not a multiple of 8", who, (long long)kv_bstride);
+    PARROT_REQUIRE(!SEQ || B <= S, "%s: M=%d rows do not fit a cache of %d slots", who, B, S);
+    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "%s: 16-byte alignment", who);
+    const AttnRowsArgs rows{ldqkv, ldy, kv_bstride};
+    hipStream_t st = (hipStream_t)stream;
+    switch (hs) {
+        case 32: return attn_fused_launch<32, false, true, SEQ>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
+                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
+        case 64: return attn_fused_launch<64, false, true, SEQ>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
+                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
+        default: return attn_fused_launch<128, false, true, SEQ>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
+                                                            nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
+    }
+}
+
+extern "C" {
+
 int parrot_attn_fused_decode_rows(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
                                   const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
                                   void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
                                   int softmax_mode, void* stream) {
-    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "attn_fused_decode_rows: B=%d (1 .. %d)", B, kMaxDecodeRows);
-    {
-        const int rc = check_softmax_mode("attn_fused_decode_rows", softmax_mode, S, nsplit);
-        if (rc != PARROT_OK) return rc;
-    }
-    PARROT_REQUIRE(qkv && pos && k_cache && v_cache && y, "attn_fused_decode_rows: null pointer");
-    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1, "attn_fused_decode_rows: bad shape");
-    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "attn_fused_decode_rows: at most %d query heads per group (got %d)", kFusedMaxQ, q_per_kv);
-    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "attn_fused_decode_rows: head size %d not built (32, 64, 128)", hs);
-    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "attn_fused_decode_rows: bad n_elem=%d", n_elem);
-    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "attn_fused_decode_rows: rope tables missing");
-    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "attn_fused_decode_rows: nsplit out of range");
-    const int n_head = n_groups * q_per_kv;
-    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "attn_fused_decode_rows: workspace and tickets required when nsplit > 1");
-    PARROT_REQUIRE(!tickets || n_tickets >= B * n_head, "attn_fused_decode_rows: %d tickets, B * n_head = %d needed", n_tickets, B * n_head);
-    PARROT_REQUIRE(ldqkv >= n_groups * (q_per_kv + 2) * hs && ldqkv % 8 == 0, "attn_fused_decode_rows: ldqkv=%d too small or not a multiple of 8", ldqkv);
-    PARROT_REQUIRE(ldy >= n_head * hs, "attn_fused_decode_rows: ldy=%d too small", ldy);
-    PARROT_REQUIRE(kv_bstride >= (int64_t)n_groups * S * hs && kv_bstride % 8 == 0,
-                   "attn_fused_decode_rows: kv_bstride=%lld below n_groups * S * hs or not a multiple of 8", (long long)kv_bstride);
-    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "attn_fused_decode_rows: 16-byte alignment");
-    const AttnRowsArgs rows{ldqkv, ldy, kv_bstride};
-    hipStream_t st = (hipStream_t)stream;
-    switch (hs) {
-        case 32: return attn_fused_launch<32, false, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
-                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
-        case 64: return attn_fused_launch<64, false, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
-                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
-        default: return attn_fused_launch<128, false, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
-                                                            nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
-    }
+    return attn_fused_rows_entry<false>("attn_fused_decode_rows", qkv, ldqkv, B, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S,
+                                        nsplit, workspace, tickets, n_tickets, k_cache, v_cache, kv_bstride, y, ldy, softmax_mode, stream);
+}
+
+int parrot_attn_fused_decode_seq(const void* qkv, int ldqkv, int M, const void* rope_cos, const void* rope_sin, int n_elem,
+                                 const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                 void* tickets, int n_tickets, void* k_cache, void* v_cache, void* y, int ldy, int softmax_mode,
+                                 void* stream) {
+    return attn_fused_rows_entry<true>("attn_fused_decode_seq", qkv, ldqkv, M, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S,
+                                       nsplit, workspace, tickets, n_tickets, k_cache, v_cache, 0, y, ldy, softmax_mode, stream);
 }
 
 // prefix K/V, gate and aT of the two adapter entry points

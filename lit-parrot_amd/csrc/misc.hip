@@ -383,6 +383,113 @@ stop_check_kernel(const int64_t* __restrict__ tokens, const int32_t* __restrict_
     }
 }
 
+
+// ------------------------------------------------------------------------------------------ prompt-lookup speculative decoding
+// Loop state beside tokens / pos, int32 words: the drafting and the verification kernel each own some of them and the host
+// reads all of them in one copy per step.
+enum SpecState : int {
+    SPEC_MATCHED = 0,   // ngram_draft: drafts of its last call that were copied from an earlier occurrence (0: no match)
+    SPEC_ACCEPTED = 1,  // verify_advance: accepted drafts, summed over its calls
+    SPEC_STEPS = 2,     // verify_advance: its calls that advanced
+    SPEC_POS = 3,       // ngram_draft: pos[0] as it saw it
+    SPEC_LAST = 4,      // ngram_draft: tokens[pos[0]] (the host's eos test)
+    SPEC_WORDS = 8
+};
+constexpr int kDraftThreads = 256;
+constexpr int kMaxDraftLen = kMaxDecodeRows - 1;
+constexpr int kMaxNgram = 16;
+
+// Prompt lookup: tokens[0 .. pos] are known.  For n = ngram_max down to ngram_min (an n longer than the sequence is skipped), find the
+// LARGEST j with j + n <= pos and tokens[j .. j+n-1] == tokens[pos-n+1 .. pos] - the last earlier occurrence of the newest n-gram -
+// and copy what followed it: draft i = tokens[j + n + i] while that index is <= pos.  Every other draft slot (all K without a match)
+// repeats tokens[pos].  The K drafts go to tokens[pos+1 .. pos+K] (slots past the buffer are dropped), beyond the valid part.
+// One workgroup; thread t walks the candidates pos-n-t, pos-n-t-256, ... downwards, so its first hit is its largest, and the
+// workgroup's answer is one max-reduction over those: the result does not depend on scheduling.
+__global__ void __launch_bounds__(kDraftThreads)
+ngram_draft_kernel(int64_t* __restrict__ tokens, int L, const int32_t* __restrict__ pos_ptr, int K, int ngram_max, int ngram_min,
+                   int32_t* __restrict__ state) {
+    __shared__ int sh_best[kDraftThreads / 64];
+    const int pos = pos_ptr[0];
+    if (pos < 0 || pos >= L) return;  // (never in the decode loop: nothing to read)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int hit_j = -1, hit_n = 0;
+    for (int n = ngram_max; n >= ngram_min; --n) {
+        if (pos - n + 1 < 0) continue;  // uniform
+        const int64_t* tail = tokens + (pos - n + 1);
+        int best = -1;
+        for (int j = pos - n - (int)threadIdx.x; j >= 0; j -= kDraftThreads) {
+            bool eq = true;
+            for (int i = n - 1; i >= 0 && eq; --i) eq = tokens[j + i] == tail[i];
+            if (eq) {
+                best = j;
+                break;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) best = max(best, __shfl_xor(best, off, 64));
+        if (lane == 0) sh_best[wave] = best;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < kDraftThreads / 64; ++w) best = max(best, sh_best[w]);
+        __syncthreads();  // (sh_best is written again for the next n)
+        if (best >= 0) {  // uniform
+            hit_j = best;
+            hit_n = n;
+            break;
+        }
+    }
+    const int64_t last = tokens[pos];
+    const int follow = hit_j + hit_n;  // first token after the earlier occurrence (<= pos when there is one)
+    if ((int)threadIdx.x < K) {
+        const int i = threadIdx.x;
+        const int64_t d = (hit_j >= 0 && follow + i <= pos) ? tokens[follow + i] : last;
+        if (pos + 1 + i < L) tokens[pos + 1 + i] = d;
+    }
+    if (threadIdx.x == 0) {
+        state[SPEC_MATCHED] = hit_j >= 0 ? min(K, pos - follow + 1) : 0;
+        state[SPEC_POS] = pos;
+        state[SPEC_LAST] = (int32_t)last;
+    }
+}
+
+// Greedy verification of the M = K + 1 rows of a speculative step: row m holds the logits of position pos + m, whose input token
+// was tokens[pos + m] (m >= 1: draft m - 1).  a_m = argmax_row(logits[m]) - the device function of argmax_advance, so the bits and
+// the tie rule are its own.  c = the number of leading drafts with a_m == tokens[pos+1+m], cut so that no token is written at or
+// past min(end, L) and, with eos_id >= 0, at the first a_m == eos_id (the eos token is written; the sequence is then frozen as
+// decode_row_frozen says, and a later call neither writes nor advances).  Then tokens[pos+1+c] = a_c, pos += c + 1.  Rows after
+// the first rejected one are not even read.  One workgroup, rows in turn.
+__global__ void __launch_bounds__(kArgmaxThreads)
+verify_advance_kernel(const bf16_t* __restrict__ logits, int V, int ldl, int vec, int M, int64_t* __restrict__ tokens, int L,
+                      int32_t* __restrict__ pos_ptr, const int32_t* __restrict__ end_ptr, int eos_id, int32_t* __restrict__ state,
+                      int32_t* __restrict__ row_pos) {
+    __shared__ int sh_more;
+    const int pos = pos_ptr[0];
+    const int stop = min(end_ptr[0], L);
+    if (decode_row_frozen(tokens, L, pos, end_ptr[0], eos_id)) {
+        if (row_pos != nullptr && (int)threadIdx.x < M) row_pos[threadIdx.x] = pos + threadIdx.x;
+        return;
+    }
+    for (int m = 0; m < M; ++m) {
+        const int bi = argmax_row(logits + (int64_t)m * ldl, V, vec);
+        if (threadIdx.x == 0) {
+            const int a = (bi == 0x7fffffff) ? 0 : bi;
+            // draft m is accepted when it is the arg-max, is not eos, and the token after it still has a slot
+            const bool more = m + 1 < M && tokens[pos + 1 + m] == (int64_t)a && !(eos_id >= 0 && a == eos_id) && pos + 2 + m < stop;
+            if (!more) {
+                tokens[pos + 1 + m] = a;  // (pos + 1 + m < stop: by the frozen test for m = 0, by `more` of row m - 1 after)
+                pos_ptr[0] = pos + m + 1;
+                state[SPEC_ACCEPTED] += m;
+                state[SPEC_STEPS] += 1;
+                if (row_pos != nullptr)
+                    for (int r = 0; r < M; ++r) row_pos[r] = pos + m + 1 + r;
+            }
+            sh_more = more;
+        }
+        __syncthreads();  // (also orders thread 0's reads of argmax_row's LDS before the next row's writes)
+        if (!sh_more) return;
+    }
+}
+
 }  // namespace parrot
 
 using namespace parrot;
@@ -478,6 +585,29 @@ int parrot_topk_sample_rows(const void* logits, int V, int ldl, int B, float tem
     if (vec && V <= 8192 * 4) PARROT_SAMPLE_ROWS_GO(4);
     PARROT_SAMPLE_ROWS_GO(0);
 #undef PARROT_SAMPLE_ROWS_GO
+}
+
+int parrot_ngram_draft(int64_t* tokens, int L, const int32_t* pos, int draft_len, int ngram_max, int ngram_min, int32_t* state,
+                       void* stream) {
+    PARROT_REQUIRE(tokens && pos && state, "ngram_draft: null pointer");
+    PARROT_REQUIRE(L >= 1, "ngram_draft: L=%d", L);
+    PARROT_REQUIRE(draft_len >= 1 && draft_len <= kMaxDraftLen, "ngram_draft: draft_len=%d (1 .. %d)", draft_len, kMaxDraftLen);
+    PARROT_REQUIRE(ngram_min >= 1 && ngram_max >= ngram_min && ngram_max <= kMaxNgram,
+                   "ngram_draft: n-grams %d .. %d (1 <= ngram_min <= ngram_max <= %d)", ngram_min, ngram_max, kMaxNgram);
+    return launch(K_NGRAM_DRAFT, ngram_draft_kernel, dim3(1), dim3(kDraftThreads), 0, (hipStream_t)stream, tokens, L, pos, draft_len,
+                  ngram_max, ngram_min, state);
+}
+
+int parrot_verify_advance(const void* logits, int V, int ldl, int M, int64_t* tokens, int L, int32_t* pos, const int32_t* end,
+                          int eos_id, int32_t* state, int32_t* row_pos, void* stream) {
+    PARROT_REQUIRE(logits && tokens && pos && end && state, "verify_advance: null pointer");
+    PARROT_REQUIRE(M >= 2 && M <= kMaxDecodeRows, "verify_advance: M=%d rows (2 .. %d: one token and 1 .. %d drafts)", M, kMaxDecodeRows,
+                   kMaxDraftLen);
+    PARROT_REQUIRE(V >= 1 && ldl >= V && L >= 2, "verify_advance: bad shape V=%d ldl=%d L=%d", V, ldl, L);
+    PARROT_REQUIRE(eos_id >= -1, "verify_advance: eos_id=%d (-1: none)", eos_id);
+    const int vec = (V >= 8 && aligned16(logits) && ldl % 8 == 0) ? 1 : 0;
+    return launch(K_VERIFY_ADVANCE, verify_advance_kernel, dim3(1), dim3(kArgmaxThreads), 0, (hipStream_t)stream, (const bf16_t*)logits,
+                  V, ldl, vec, M, tokens, L, pos, end, eos_id, state, row_pos);
 }
 
 }  // extern "C"

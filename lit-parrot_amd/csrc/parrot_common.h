@@ -102,6 +102,9 @@ enum KernelId : int {
     K_ARGMAX_ROWS,
     K_TOPK_SAMPLE_ROWS,
     K_ATTN_FUSED_ROWS,
+    K_ATTN_FUSED_SEQ,
+    K_NGRAM_DRAFT,
+    K_VERIFY_ADVANCE,
     K_COUNT
 };
 
@@ -208,6 +211,29 @@ __device__ __forceinline__ float wave_sum8(const float (&p)[8]) {
     w += dpp0<0xB1>(w);                     // quad_perm [1,0,3,2]
     w += dpp0<0x4E>(w);                     // quad_perm [2,3,0,1]
     return w;
+}
+// wave_sum_to_lane63(s * d) as the compiler contracts it in the one-row GEMV kernels (-ffp-contract=fast): the first step adds the
+// neighbour's ROUNDED product to this lane's product inside one fma.  Written out so that a kernel that must reproduce those bits
+// does not depend on the contraction being found again.
+__device__ __forceinline__ float wave_sum_prod_to_lane63(float s, float d) {
+    float v = __fmaf_rn(s, d, dpp0<0xB1>(__fmul_rn(s, d)));  // quad_perm [1,0,3,2]
+    v += dpp0<0x4E>(v);        // quad_perm [2,3,0,1]
+    v += dpp0<0x141>(v);       // row_half_mirror
+    v += dpp0<0x140>(v);       // row_mirror
+    v += dpp0<0x142, 0xA>(v);  // row_bcast15 into rows 1 and 3
+    v += dpp0<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3
+    return v;
+}
+// One wave sum with the additions of wave_sum8 in wave_sum8's order (lower + upper 32 lanes, even + odd 16-lane row, lanes 8
+// apart, then inside the 8 lanes): bit for bit the total wave_sum8 returns for the same 64 values; every lane gets it.
+__device__ __forceinline__ float wave_sum_order8(float v) {
+    v = swap_add32(v, v);
+    v = swap_add16(v, v);
+    v += dpp0<0x128>(v);  // row_ror:8
+    v += dpp0<0x141>(v);  // row_half_mirror
+    v += dpp0<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp0<0x4E>(v);   // quad_perm [2,3,0,1]
+    return v;
 }
 __device__ __forceinline__ int wave_sum_i32_to_lane63(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);

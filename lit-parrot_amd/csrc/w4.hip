@@ -126,7 +126,8 @@ template <int M, bool DUAL, int RU, int MAXW, bool CB>
 __global__ void __launch_bounds__(MAXW * 64)
 w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const bf16_t* __restrict__ x, int ldx,
                const bf16_t* __restrict__ bias, const bf16_t* residual, int ldr, bf16_t* out, int ldo, int N, int K,
-               int wps, int epi, int iters, NormArgs na, W4Plan plan, unsigned long long* dbg, const uint32_t* __restrict__ code) {
+               int wps, int epi, int iters, NormArgs na, W4Plan plan, unsigned long long* dbg, const uint32_t* __restrict__ code,
+               int order8) {
     constexpr int NW = DUAL ? 2 : 1;
     __shared__ __attribute__((aligned(4096))) uint32_t cbt[CB ? 16 * 64 : 1];
     extern __shared__ __attribute__((aligned(16))) unsigned char w4_smem[];  // normalised activations [M][K] bf16 (norm only)
@@ -331,6 +332,19 @@ w4_gemv_kernel(const uint4* __restrict__ W, const uint4* __restrict__ W2, const 
                 if constexpr (CB) w4c_slice_lookup(w[q][u], cb_col, wcb);  // once per weight row, shared by the M input rows
 #pragma unroll
                 for (int m = 0; m < M; ++m) {
+                    if constexpr (M > 1) {
+                        // A row must come out bit for bit as the one-row launch of this Linear computes it, so the scaled product
+                        // and its lane sum are spelled out here instead of being left to the compiler's contraction: the one-row
+                        // kernel rounds s * d and sums with wave_sum8 where it takes 8 rows per wave (order8, uniform), and
+                        // elsewhere fuses the product into the first step of wave_sum_to_lane63.
+                        float d;
+                        if constexpr (CB)
+                            d = w4c_pairs_dot(wcb, xr[m]);
+                        else
+                            d = w4_slice_dot(w[q][u], xr[m]) - zz * xs[m];
+                        part[q][m] = order8 ? wave_sum_order8(__fmul_rn(s, d)) : wave_sum_prod_to_lane63(s, d);
+                        continue;
+                    }
                     float v;
                     if constexpr (CB)
                         v = s * w4c_pairs_dot(wcb, xr[m]);
@@ -402,7 +416,7 @@ static int pick_wps(int N, int RU, int nslabs, int maxw, bool norm) {
 template <int M, bool DUAL, int RU, int MAXW, bool CB>
 static int w4_gemv_launch_v(const void* packed, const void* packed2, const void* x, int ldx, const void* bias,
                             const void* residual, int ldr, void* out, int ldo, int N, int K, int epi, const NormArgs& na,
-                            const W4Plan& plan, hipStream_t st, const void* code) {
+                            const W4Plan& plan, hipStream_t st, const void* code, int order8 = 0) {
     const int wps = pick_wps(N, RU, plan.nslabs, MAXW, na.kind != 0);
     const int nthreads = 64 * plan.nslabs * wps;
     size_t lds;
@@ -416,7 +430,7 @@ static int w4_gemv_launch_v(const void* packed, const void* packed2, const void*
                   w4_gemv_kernel<M, DUAL, RU, MAXW, CB>, grid, block, lds, st,
                   (const uint4*)packed, (const uint4*)packed2, (const bf16_t*)x, ldx, (const bf16_t*)bias,
                   (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, N, K, wps, epi, g.iters, na, plan, g_w4_dbg_host,
-                  (const uint32_t*)code);
+                  (const uint32_t*)code, order8);
 }
 
 template <int M, bool CB>
@@ -427,8 +441,13 @@ static int w4_gemv_launch(const void* packed, const void* packed2, const void* x
     constexpr int RU1 = (M == 1) ? 8 : 4;  // (16 / 8 rows in flight measured slower: occupancy drops to 3 waves per SIMD)
     // (codebook weights: the 32 raw lookups of a slice live beside the weights: 8 x 2 rows would take 168 VGPRs, 3 waves per SIMD)
     constexpr int RU2 = (M == 1) ? (CB ? 4 : 8) : ((M <= 2) ? 4 : 2);  // M = 1: 8 rows x 2 weights per wave measured 3 % faster end to end than 4
+    // A row of a multi-row launch must come out bit for bit as the one-row launch of the same Linear computes it (batched and
+    // speculative decode compare rows with the one-row step): where that launch takes 8 rows per wave it sums the lanes with
+    // wave_sum8, whose additions associate differently from wave_sum_to_lane63's, so the multi-row kernel adds in that order there.
+    const bool m1_sum8 = plan.nslabs <= 8 && (epi == PARROT_EPI_SWIGLU ? !CB : (int64_t)N * plan.nslabs > 8192 * 2);
+    const int order8 = (M > 1 && m1_sum8) ? 1 : 0;
 #define PARROT_W4_GO(DUALV, RUV, MAXWV) \
-    return w4_gemv_launch_v<M, DUALV, RUV, MAXWV, CB>(packed, packed2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, plan, st, code)
+    return w4_gemv_launch_v<M, DUALV, RUV, MAXWV, CB>(packed, packed2, x, ldx, bias, residual, ldr, out, ldo, N, K, epi, na, plan, st, code, order8)
     if (plan.nslabs <= 8) {
         if (epi == PARROT_EPI_SWIGLU) PARROT_W4_GO(true, RU2, 8);
         // small single-row launches (the attention out-projection: N x slabs <= 16 K): 4 rows per wave, twice the waves -

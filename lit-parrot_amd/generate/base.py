@@ -417,3 +417,214 @@ def generate_batch(
             n -= 1  # the reference returns idx[:input_pos]: the eos token is not part of the result
         out.append(sess.tokens[b, :n].to(p.dtype).clone())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ speculative decode
+class SpeculativeSession:
+    """Greedy decoding of ONE sequence that verifies ``draft_len`` guessed tokens per weight pass (prompt-lookup speculative
+    decoding).  The drafts are what followed the last earlier occurrence of the sequence's newest n-gram (``ops.ngram_draft``); the
+    token at ``pos`` and the K drafts behind it go through the network as the M = K + 1 rows of one pass, every row bit for bit
+    what the one-row step computes for it, and ``ops.verify_advance`` keeps the drafts that are the arg-max of the row before them.
+    The tokens are therefore exactly ``generate(top_k=1)``'s; only the number of steps changes.
+
+        tokens  int64[max_tokens + 1]   the prompt, the generated tokens and, behind ``pos``, the current drafts
+        pos     int32[1]                position of the newest known token
+        end     int32[1]                no token is written at or past it (max_returned_tokens)
+        state   int32[8]                ops.SPEC_*: what the host reads once per step
+
+    Two steps are captured over these buffers, each ending with the drafting for the next one:
+        rows:  M-row pass -> verify_advance -> ngram_draft          one:  one-row pass -> argmax_advance -> ngram_draft
+    ``generate_speculative`` replays ``rows`` when the last drafting found an earlier occurrence and ``pos + M`` stays inside the
+    token buffer, the cache and the RoPE tables, else ``one``: no row is ever computed at a position outside them.
+
+    ``draft_hook(session) -> int``, when given, replaces the lookup kernel: it writes ``tokens[pos+1 .. pos+K]`` and returns how
+    many of them are guesses (0: take the one-row step).  It runs on the host between the replays, outside the captured steps."""
+
+    def __init__(self, model: GPT, max_seq_length: int, max_tokens: int, draft_len: int = 1, ngram_max: int = 3, ngram_min: int = 1,
+                 eos_id: int = -1, use_graph: bool = True, draft_hook: Optional[Callable[["SpeculativeSession"], int]] = None) -> None:
+        if not 1 <= draft_len <= ops.MAX_DRAFT_LEN:
+            raise ParrotHipError(f"draft_len={draft_len}: the speculative step verifies 1 to {ops.MAX_DRAFT_LEN} drafts")
+        if not 1 <= ngram_min <= ngram_max <= ops.MAX_NGRAM:
+            raise ParrotHipError(f"n-grams {ngram_min} .. {ngram_max}: 1 <= ngram_min <= ngram_max <= {ops.MAX_NGRAM} expected")
+        dev = model.transformer.wte.weight.device
+        if dev.type != "cuda":
+            raise ParrotHipError("generate_speculative() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+        why = model.speculative_decode_unsupported()
+        if why is not None:
+            raise ParrotHipError(f"speculative decode: {why}")
+        if max_seq_length < max_tokens:
+            raise ParrotHipError(f"speculative decode: a window of {max_seq_length} slots is shorter than the {max_tokens} tokens: the "
+                                 "rows of a step must not wrap the cache ring")
+        self.model, self.S, self.K, self.M = model, max_seq_length, draft_len, draft_len + 1
+        self.ngram_max, self.ngram_min, self.eos_id, self.draft_hook = ngram_max, ngram_min, eos_id, draft_hook
+        self.device = dev
+        self.tokens = torch.zeros((max_tokens + 1,), dtype=torch.int64, device=dev)
+        self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.end = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.state = torch.zeros((ops.SPEC_STATE_WORDS,), dtype=torch.int32, device=dev)
+        self.ws_one = model.workspace(1, dev, 1)
+        self.ws_rows = model.workspace(self.M, dev, self.M, rows_are_drafts=True)
+        self.graphs: Dict[bool, torch.cuda.CUDAGraph] = {}  # True: the M-row step, False: the one-row step
+        self.use_graph = use_graph
+        if model.rope_cache is None:
+            model.rope_cache = model.build_rope_cache(self.tokens)
+        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != 1:
+            model.kv_caches = model.build_kv_caches(self.tokens.view(1, -1), max_seq_length, model.rope_cache[0].size(-1))
+        self.caches = [(k[0], v[0]) for k, v in model.kv_caches]
+        if RELEASE_REFERENCE_BUFFERS:
+            for m in model.modules():
+                if hasattr(m, "release_reference"):
+                    m.release_reference()
+
+    def draft(self) -> None:
+        """The lookup kernel (the hook, when there is one, is called by the loop instead: it is host code)."""
+        if self.draft_hook is None:
+            ops.ngram_draft(self.tokens, self.pos, self.K, self.ngram_max, self.ngram_min, self.state)
+
+    def _step_rows(self) -> torch.Tensor:
+        logits = self.model.run_rows(self.ws_rows, self.tokens, self.pos, self.pos, self.S, self.caches, self.model.rope_cache)
+        ops.verify_advance(logits, self.tokens, self.pos, self.end, self.eos_id, self.state)
+        self.draft()
+        return logits
+
+    def _step_one(self) -> torch.Tensor:
+        logits = self.model.run_rows(self.ws_one, self.tokens, self.pos, self.pos, self.S, self.caches, self.model.rope_cache)
+        ops.argmax_advance(logits, self.tokens, self.pos)
+        self.draft()
+        return logits
+
+    def prefill(self, prompt: torch.Tensor, max_returned_tokens: int) -> torch.Tensor:
+        """Run the T prompt rows, leave ``pos`` = T-1 and return the logits of the last prompt token (DecodeSession.prefill)."""
+        T = prompt.numel()
+        self.tokens[:T].copy_(prompt)
+        self.pos.zero_()
+        self.end.fill_(max_returned_tokens)
+        self.state.zero_()
+        ws = self.model.workspace(T, self.device, 1)
+        ws.pos_is_zero = True
+        try:
+            logits = self.model.run_rows(ws, self.tokens, None, self.pos, self.S, self.caches, self.model.rope_cache)
+        finally:
+            ws.pos_is_zero = False
+        self.pos.fill_(T - 1)
+        return logits
+
+    def capture(self, rows: bool = True) -> None:
+        """Capture the one-row step and, with ``rows``, the M-row step (each once).  The warm-up runs at the position the prompt
+        left: the caller passes ``rows`` only when ``pos + M`` is inside every buffer there."""
+        if not self.use_graph:
+            return
+        # warm-up outside capture and restore of the loop state afterwards, as DecodeSession.capture
+        saved = (self.tokens.clone(), self.pos.clone(), self.state.clone(), [(k.clone(), v.clone()) for k, v in self.caches])
+
+        def restore() -> None:
+            self.tokens.copy_(saved[0])
+            self.pos.copy_(saved[1])
+            self.state.copy_(saved[2])
+            for (k, v), (k0, v0) in zip(self.caches, saved[3]):
+                k.copy_(k0)
+                v.copy_(v0)
+
+        for is_rows, step in ((True, self._step_rows), (False, self._step_one)):
+            if is_rows in self.graphs or (is_rows and not rows):
+                continue
+            side = torch.cuda.Stream(device=self.device)
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(side):
+                step()
+            torch.cuda.current_stream(self.device).wait_stream(side)
+            torch.cuda.synchronize(self.device)
+            restore()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                step()
+            self.graphs[is_rows] = graph
+            restore()
+
+    def step(self, rows: bool) -> torch.Tensor:
+        """One step: the M-row verification pass (``rows``) or the one-row step; returns that pass's logits buffer."""
+        if self.use_graph:
+            self.graphs[rows].replay()
+            return self.ws_rows.logits if rows else self.ws_one.logits
+        return self._step_rows() if rows else self._step_one()
+
+    def read(self, hook_matched: int = 0) -> Tuple[int, int, int]:
+        """The step's one host read: (pos, drafts the last drafting matched, tokens[pos])."""
+        if self.draft_hook is None:
+            st = self.state.cpu()
+            return int(st[ops.SPEC_POS]), int(st[ops.SPEC_MATCHED]), int(st[ops.SPEC_LAST])
+        p = int(self.pos)
+        return p, hook_matched, int(self.tokens[p])
+
+
+@torch.no_grad()
+def generate_speculative(
+    model: torch.nn.Module,
+    idx: torch.Tensor,
+    max_returned_tokens: int,
+    max_seq_length: int,
+    *,
+    draft_len: int = 1,
+    ngram_max: int = 3,
+    ngram_min: int = 1,
+    eos_id: Optional[int] = None,
+    return_stats: bool = False,
+    draft_hook: Optional[Callable[[SpeculativeSession], int]] = None,
+):
+    """What ``generate(model, idx, max_returned_tokens, max_seq_length, top_k=1, eos_id=eos_id)`` returns, token for token, in
+    fewer weight passes: every step verifies ``draft_len`` tokens guessed by prompt lookup (SpeculativeSession) next to the one it
+    decodes.  Greedy only - rejection sampling would not reproduce the reference's draws.  With ``return_stats`` the result is
+    ``(tokens, {"steps": weight passes after the prompt, "accepted": drafts kept, "matched_steps": passes that verified drafts})``.
+    ``draft_hook`` (tests, tools/spec_bench.py) replaces the lookup, see SpeculativeSession."""
+    T = idx.size(0)
+    assert max_returned_tokens > T
+    if not isinstance(model, GPT):
+        raise ParrotHipError("generate_speculative() drives lit_parrot_amd.GPT models")
+    assert max_seq_length <= model.config.block_size
+    if max_returned_tokens > model.config.block_size:
+        raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
+                             "positions past the RoPE tables")
+    assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
+    if not 1 <= draft_len <= ops.MAX_DRAFT_LEN:
+        raise ParrotHipError(f"draft_len={draft_len}: the speculative step verifies 1 to {ops.MAX_DRAFT_LEN} drafts")
+    if not 1 <= ngram_min <= ngram_max <= ops.MAX_NGRAM:
+        raise ParrotHipError(f"n-grams {ngram_min} .. {ngram_max}: 1 <= ngram_min <= ngram_max <= {ops.MAX_NGRAM} expected")
+    why = model.speculative_decode_unsupported()
+    if why is not None:
+        raise ParrotHipError(f"generate_speculative: {why}; use generate()")
+    if max_seq_length < max_returned_tokens:
+        raise ParrotHipError(f"generate_speculative: max_seq_length={max_seq_length} < max_returned_tokens={max_returned_tokens}: the "
+                             "rows of a speculative step must not wrap the cache ring (no sliding window); use generate()")
+    if model.transformer.wte.weight.device.type != "cuda":
+        raise ParrotHipError("generate_speculative() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    eos = -1 if eos_id is None else int(eos_id)
+    make = lambda: SpeculativeSession(model, max_seq_length, max_returned_tokens, draft_len, ngram_max, ngram_min, eos,  # noqa: E731
+                                      draft_hook=draft_hook)
+    if draft_hook is not None:
+        sess = make()  # (a hook is the caller's object: its session is not kept)
+    else:
+        sess = _cached_session(model, ("speculative", max_seq_length, draft_len, ngram_max, ngram_min, eos), max_returned_tokens, make)
+    M = sess.M
+    limit = min(max_returned_tokens, max_seq_length, model.config.block_size)  # rows at pos .. pos+M-1 need pos + M <= limit
+    dtype = idx.dtype
+    logits = sess.prefill(idx.to(device=sess.device, dtype=torch.int64), max_returned_tokens)
+    sess.capture(rows=T - 1 + M <= limit)  # (a prompt that ends within M of the limit never takes the M-row step)
+    ops.argmax_advance(logits, sess.tokens, sess.pos)  # the first token, as generate() samples it
+    sess.draft()
+    steps = matched_steps = hook_matched = 0
+    while True:
+        if draft_hook is not None:
+            hook_matched = int(draft_hook(sess))
+        p, matched, last = sess.read(hook_matched)  # host sync, the one generate() pays with eos_id
+        stop_eos = eos_id is not None and last == eos
+        if stop_eos or p + 1 >= max_returned_tokens:
+            break
+        rows = matched > 0 and p + M <= limit
+        sess.step(rows)
+        steps += 1
+        matched_steps += int(rows)
+    # generate() returns idx[:input_pos]: the eos token is not part of the result
+    out = sess.tokens[: p if stop_eos else p + 1].to(dtype).clone()
+    if return_stats:
+        return out, {"steps": steps, "accepted": int(sess.state[ops.SPEC_ACCEPTED]), "matched_steps": matched_steps}
+    return out

@@ -51,14 +51,18 @@ class Workspace:
     """Every intermediate of ``M`` token rows through the network (allocated once per M).
 
     ``rows_are_sequences``: batched decode - row b is the one new token of sequence b (its own position and KV cache), not
-    position ``pos + b`` of one sequence."""
+    position ``pos + b`` of one sequence.
+    ``rows_are_drafts``: speculative decode - the rows are positions ``pos .. pos + M - 1`` of one sequence, as in a prompt, but
+    every row must come out bit for bit as the one-row step computes it: its attention is the fused decode kernel's
+    (``ops.attn_fused_decode_seq``), not the prompt kernels'."""
 
-    def __init__(self, config: Config, M: int, device, lm_rows: int, rows_are_sequences: bool = False) -> None:
+    def __init__(self, config: Config, M: int, device, lm_rows: int, rows_are_sequences: bool = False,
+                 rows_are_drafts: bool = False) -> None:
         def buf(cols: int, rows: int = M) -> torch.Tensor:
             return torch.empty((rows, cols), dtype=torch.bfloat16, device=device)
 
         c = config
-        self.M, self.lm_rows, self.rows_are_sequences = M, lm_rows, rows_are_sequences
+        self.M, self.lm_rows, self.rows_are_sequences, self.rows_are_drafts = M, lm_rows, rows_are_sequences, rows_are_drafts
         self.x, self.t = buf(c.n_embd), buf(c.n_embd)
         self.qkv = buf(c.qkv_size)
         self.q = buf(c.n_head * c.head_size)
@@ -67,8 +71,8 @@ class Workspace:
         self.logits = buf(c.padded_vocab_size, lm_rows)
         self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=device)
         self.side_stream = None  # parallel-residual blocks: the MLP's first Linear runs beside the attention branch
-        # fused attention arrival counters (n_head per sequence)
-        self.tickets = torch.zeros((M * c.n_head if rows_are_sequences else c.n_head,), dtype=torch.int32, device=device)
+        # fused attention arrival counters (n_head per sequence / per draft row)
+        self.tickets = torch.zeros((M * c.n_head if rows_are_sequences or rows_are_drafts else c.n_head,), dtype=torch.int32, device=device)
         self._attn_ws = {}
 
     def attn_ws(self, config: Config, nsplit: int) -> torch.Tensor:
@@ -203,13 +207,14 @@ class GPT(nn.Module):
             for _ in range(c.n_layer)
         ]
 
-    def workspace(self, M: int, device, lm_rows: Optional[int] = None, rows_are_sequences: bool = False) -> Workspace:
+    def workspace(self, M: int, device, lm_rows: Optional[int] = None, rows_are_sequences: bool = False,
+                  rows_are_drafts: bool = False) -> Workspace:
         lm_rows = M if lm_rows is None else lm_rows
-        key = (M, lm_rows, str(device)) + (("rows",) if rows_are_sequences else ())
+        key = (M, lm_rows, str(device)) + (("rows",) if rows_are_sequences else ()) + (("drafts",) if rows_are_drafts else ())
         if key not in self._workspaces:
             if len(self._workspaces) > 8:
                 self._workspaces.clear()
-            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows_are_sequences)
+            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows_are_sequences, rows_are_drafts)
         return self._workspaces[key]
 
     def batched_decode_unsupported(self) -> Optional[str]:
@@ -229,6 +234,23 @@ class GPT(nn.Module):
             return f"head size {c.head_size}: the batched attention is built for 32, 64 and 128"
         return None
 
+    def speculative_decode_unsupported(self) -> Optional[str]:
+        """Why the speculative decode step (``Workspace(rows_are_drafts=True)``: a token and its drafts as the rows of one pass, each
+        row bit for bit the one-row step) cannot run this model, or None when it can."""
+        from .quantize.bnb import InferenceLinear8bitLt
+
+        c = self.config
+        if any(isinstance(m, InferenceLinear8bitLt) for m in self.modules()):
+            return ("LLM.int8 Linears: the multi-row activation quantiser takes the outlier columns of all rows together, so a "
+                    "verified row would not equal the one-row step")
+        if hasattr(self, "adapter_kv_caches") or any(hasattr(m, "adapter_scale") or hasattr(m, "adapter_bias") for m in self.modules()):
+            return "adapter models: the prefix / adapter-v2 terms are built for the one-row step"
+        if c.q_per_kv > ops.FUSED_ATTN_MAX_Q_PER_KV:
+            return f"{c.q_per_kv} query heads per K/V group: the fused decode attention is built for at most {ops.FUSED_ATTN_MAX_Q_PER_KV}"
+        if c.head_size not in (32, 64, 128):
+            return f"head size {c.head_size}: the fused decode attention is built for 32, 64 and 128"
+        return None
+
     # ------------------------------------------------------------------------------------------ execution
     def run_rows(self, ws: Workspace, tokens: torch.Tensor, tok_pos: Optional[torch.Tensor], pos: torch.Tensor,
                  S: int, caches: List[KVCache], rope: RoPECache, *, rope_local: bool = False) -> torch.Tensor:
@@ -238,6 +260,7 @@ class GPT(nn.Module):
         ``ws.logits``: all rows, or only the last row when the workspace was built with ``lm_rows == 1``.
         Batched decode (``ws.rows_are_sequences``): row b embeds ``tokens[b, tok_pos[b]]`` (``tokens[b, 0]`` without tok_pos)
         at position ``pos[b]`` (int32[M]); ``caches[i]`` are the (M, n_groups, S, hs) caches of the M sequences.
+        Speculative decode (``ws.rows_are_drafts``): the arguments of a prompt; the caller keeps ``pos + M`` inside the window.
         """
         M = ws.M
         if ws.rows_are_sequences:
@@ -245,7 +268,8 @@ class GPT(nn.Module):
             nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, 1)  # each row splits as one sequence does
         else:
             ops.embedding(self.transformer.wte.weight.data, tokens, tok_pos, M, ws.x)
-            nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, M)
+            # (draft rows split as the one-row step does: the same partial sums in the same order)
+            nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, 1 if ws.rows_are_drafts else M)
         for block, (kc, vc) in zip(self.transformer.h, caches):
             block.run_rows(ws, pos, S, kc, vc, rope, nsplit, rope_local)
         last = ws.x if ws.lm_rows == M else ws.x[M - 1:M]
@@ -396,6 +420,13 @@ class CausalSelfAttention(nn.Module):
                 raise ParrotHipError("the batched decode step has no adapter-prefix term: adapter models decode one sequence at a time")
             return ops.attn_fused_decode_rows(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv,
                                               c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
+        if ws.rows_are_drafts:  # speculative decode: append the K/V rows of all rows, then every row through the fused decode kernel
+            if prefix is not None or rope_local:
+                raise ParrotHipError("the speculative decode step has no adapter-prefix term and takes absolute positions")
+            ops.rope_kvappend(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, c.n_query_groups, c.q_per_kv, c.head_size, S,
+                              ws.q, k_cache, v_cache, False)
+            return ops.attn_fused_decode_seq(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv,
+                                             c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
         if ws.M == 1 and not rope_local and c.q_per_kv <= ops.FUSED_ATTN_MAX_Q_PER_KV:
             if prefix is not None:  # LLaMA-Adapter layer (adapter.py): the gated prefix term inside the same launch
                 return ops.attn_fused_decode_adapter(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,

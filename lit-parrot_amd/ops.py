@@ -417,6 +417,29 @@ def attn_fused_decode_rows(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
     return y
 
 
+def attn_fused_decode_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_elem: int, pos: torch.Tensor,
+                          k_cache: torch.Tensor, v_cache: torch.Tensor, n_groups: int, q_per_kv: int, hs: int, S: int,
+                          nsplit: int, workspace: torch.Tensor, tickets: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Speculative decode: row m of ``qkv`` is the token at position ``pos[0] + m`` of ONE sequence and attends to slots
+    ``0 .. pos[0] + m`` of its caches (n_groups, S, hs).  The K/V rows of all M rows must already be in the caches
+    (``rope_kvappend`` over the same rows first); the caller rules out ``pos[0] + M > S``.  Row m equals the m-th of M consecutive
+    ``attn_fused_decode`` calls with the same ``nsplit``, bit for bit."""
+    _rows(qkv, "attn_fused_decode_seq"), _rows(y, "attn_fused_decode_seq")
+    M = qkv.shape[0]
+    if pos.dtype != torch.int32 or pos.numel() != 1:
+        raise ParrotHipError("attn_fused_decode_seq: pos must be int32[1], the position of row 0")
+    for c in (k_cache, v_cache):
+        if c.dtype != torch.bfloat16 or tuple(c.shape) != (n_groups, S, hs) or not c.is_contiguous():
+            raise ParrotHipError(f"attn_fused_decode_seq: caches must be contiguous bf16 (n_groups, S, hs), got {tuple(c.shape)}")
+    if y.shape[0] != M or tickets.dtype != torch.int32:
+        raise ParrotHipError("attn_fused_decode_seq: y (M, n_head * hs) and int32 tickets expected")
+    check(_hip.load().parrot_attn_fused_decode_seq(ptr(qkv), qkv.stride(0), M, ptr(cos), ptr(sin), n_elem, ptr(pos), n_groups, q_per_kv,
+                                                   hs, S, nsplit, ptr(workspace), ptr(tickets), tickets.numel(), ptr(k_cache),
+                                                   ptr(v_cache), ptr(y), y.stride(0), ATTN_SOFTMAX_MODE, stream()),
+          "parrot_attn_fused_decode_seq")
+    return y
+
+
 class AdapterPrefix:
     """The LLaMA-Adapter prefix of one layer (lit_gpt/adapter.py:226-254): keys / values (n_groups, aT, hs) bf16 - no RoPE,
     GQA-native - and the per-head gate (n_head,) bf16 (``gating_factor``)."""
@@ -526,6 +549,53 @@ def argmax_advance(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor
         raise ParrotHipError("argmax_advance: logits bf16, tokens int64, pos int32 expected")
     check(_hip.load().parrot_argmax_advance(ptr(logits), logits.numel(), ptr(tokens), ptr(pos), stream()),
           "parrot_argmax_advance")
+
+
+# ---- prompt-lookup speculative decoding (generate/base.py::SpeculativeSession)
+MAX_DRAFT_LEN = GEMV_MAX_ROWS - 1  # one verified token + the drafts fill the M <= 8 rows of the multi-row Linears
+MAX_NGRAM = 16  # longest n-gram the lookup compares
+SPEC_STATE_WORDS = 8  # int32 loop state of the two kernels below (include/parrot_hip.h)
+SPEC_MATCHED, SPEC_ACCEPTED, SPEC_STEPS, SPEC_POS, SPEC_LAST = 0, 1, 2, 3, 4
+
+
+def _spec_args(what: str, tokens: torch.Tensor, pos: torch.Tensor, state: torch.Tensor) -> int:
+    if tokens.dtype != torch.int64 or tokens.dim() != 1 or not tokens.is_contiguous():
+        raise ParrotHipError(f"{what}: tokens must be a contiguous int64 vector")
+    if pos.dtype != torch.int32 or pos.numel() != 1:
+        raise ParrotHipError(f"{what}: pos must be int32[1]")
+    if state.dtype != torch.int32 or state.numel() < SPEC_STATE_WORDS or not state.is_contiguous():
+        raise ParrotHipError(f"{what}: state must be a contiguous int32 vector of {SPEC_STATE_WORDS} words")
+    return tokens.numel()
+
+
+def ngram_draft(tokens: torch.Tensor, pos: torch.Tensor, draft_len: int, ngram_max: int, ngram_min: int, state: torch.Tensor) -> None:
+    """Prompt lookup: ``tokens[pos+1 .. pos+draft_len]`` = what followed the last earlier occurrence of the newest n-gram
+    (``ngram_max`` down to ``ngram_min`` tokens ending at ``pos``), padded with ``tokens[pos]``; ``state[SPEC_MATCHED]`` = the
+    number of copied drafts, ``state[SPEC_POS]`` / ``state[SPEC_LAST]`` = ``pos`` / ``tokens[pos]`` for the host's one read."""
+    L = _spec_args("ngram_draft", tokens, pos, state)
+    if not 1 <= draft_len <= MAX_DRAFT_LEN:
+        raise ParrotHipError(f"ngram_draft: draft_len={draft_len}; 1 to {MAX_DRAFT_LEN} drafts")
+    if not 1 <= ngram_min <= ngram_max <= MAX_NGRAM:
+        raise ParrotHipError(f"ngram_draft: n-grams {ngram_min} .. {ngram_max}: 1 <= ngram_min <= ngram_max <= {MAX_NGRAM} expected")
+    check(_hip.load().parrot_ngram_draft(ptr(tokens), L, ptr(pos), int(draft_len), int(ngram_max), int(ngram_min), ptr(state), stream()),
+          "parrot_ngram_draft")
+
+
+def verify_advance(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, end: torch.Tensor, eos_id: int, state: torch.Tensor,
+                   row_pos: Optional[torch.Tensor] = None) -> None:
+    """Greedy verification of the M = draft_len + 1 rows of ``logits`` (row m: position ``pos + m``): accept the leading drafts
+    ``tokens[pos+1+m]`` that equal the rows' arg-max, write the first token that differs (or the one after the last draft) and
+    advance ``pos`` past it; cut at ``end`` and after ``eos_id`` (-1: none) as argmax_advance_rows freezes a row."""
+    L = _spec_args("verify_advance", tokens, pos, state)
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1 or not 2 <= logits.shape[0] <= GEMV_MAX_ROWS:
+        raise ParrotHipError(f"verify_advance: logits must be bf16 rows (M, V) with 2 <= M <= {GEMV_MAX_ROWS}")
+    M = logits.shape[0]
+    if end.dtype != torch.int32 or end.numel() != 1:
+        raise ParrotHipError("verify_advance: end must be int32[1]")
+    if row_pos is not None and (row_pos.dtype != torch.int32 or row_pos.numel() < M or not row_pos.is_contiguous()):
+        raise ParrotHipError("verify_advance: row_pos must be a contiguous int32 vector of M entries")
+    check(_hip.load().parrot_verify_advance(ptr(logits), logits.shape[1], logits.stride(0), M, ptr(tokens), L, ptr(pos), ptr(end),
+                                            int(eos_id), ptr(state), ptr(row_pos), stream()), "parrot_verify_advance")
 
 
 def topk_sample(logits: torch.Tensor, temperature: float, top_k: Optional[int], noise: torch.Tensor, tokens: torch.Tensor,
