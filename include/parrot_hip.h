@@ -246,6 +246,20 @@ int parrot_attn_fused_decode_seq(const void* qkv, int ldqkv, int M, const void* 
                                  const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
                                  void* tickets, int n_tickets, void* k_cache, void* v_cache, void* y, int ldy, int softmax_mode,
                                  void* stream);
+/* Candidates: the batched step for B rows (1 <= B <= 8) that continue ONE prompt of T = prefix_len[0] tokens (device int32[1]; one
+ * captured launch serves every T).  Replaces n prefills and n cache copies of the reference's candidate loop
+ * (`for _ in range(return_candidates): generate(...)`, the fork's straight_inference.py:218).  Row b at position pos[b] >= T attends to
+ * logical slots 0 .. pos[b]: a slot s < T is read from the one shared cache k/v_cache [n_groups][S][hs] at s, a slot s >= T from the
+ * row's tail k/v_tail [B][n_groups][S_tail][hs] at s - T, and the new K/V row is appended to the tail at pos[b] - T.  No ring: the
+ * caller keeps pos[b] < S and pos[b] - T < S_tail (the kernel clamps T to [0, S], pos to [0, S-1] and the tail index to
+ * [0, S_tail-1], so no address leaves the buffers).  Split geometry, workspace, tickets and limits as parrot_attn_fused_decode_rows:
+ * y and every appended row are bit for bit what that call computes on B full caches that each hold a copy of the prompt.
+ * share_loads != 0 (q_per_kv <= 2, nsplit > 1, B > 1): a launch in front serves the splits that lie entirely below T with one
+ * workgroup per 4 / q_per_kv rows, each K/V row loaded once for all of them; the same bits either way.                          */
+int parrot_attn_fused_decode_prefix(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                    const int32_t* pos, const int32_t* prefix_len, int n_groups, int q_per_kv, int hs, int S, int nsplit,
+                                    void* workspace, void* tickets, int n_tickets, const void* k_cache, const void* v_cache, void* k_tail,
+                                    void* v_tail, int S_tail, void* y, int ldy, int share_loads, int softmax_mode, void* stream);
 /* LLaMA-Adapter prefix attention (lit_gpt/adapter.py:226-254) in the same launch: ak / av [n_groups][aT][hs] bf16 (the
  * prefix keys / values: no RoPE), gate [n_head] bf16 (gating_factor), 1 <= aT <= 64.  The workgroup that writes y attends
  * every roped query head to all aT prefix keys (own softmax, scale 1/sqrt(hs)) and writes

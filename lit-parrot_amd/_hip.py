@@ -100,6 +100,7 @@ SIGNATURES = {
     "parrot_attn_fused_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "parrot_attn_fused_decode_rows": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i, _i, _vp]),
     "parrot_attn_fused_decode_seq": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "parrot_attn_fused_decode_prefix": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "parrot_attn_fused_decode_adapter": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "parrot_attn_adapter_prefix": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "parrot_attn_prefill_scratch_elems": (_i64, [_i, _i, _i]),

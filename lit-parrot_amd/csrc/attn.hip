@@ -869,6 +869,369 @@ static int attn_launch(const void* q, int M, const int32_t* pos, const void* k_c
                   nsplit, (bf16_t*)y, ldy, n_groups * q_per_kv);
 }
 
+// ------------------------------------------------------------------------------------------ candidates: one shared prompt cache
+// parrot_attn_fused_decode_prefix: B rows continue ONE prompt of T tokens.  The logical window of row b, slots 0 .. pos[b], is the
+// shared cache (slots < T, written once by the prompt) followed by the row's own tail (slot s >= T at tail[b][s - T]); the new K/V
+// row goes to the tail.  The split geometry is the rows kernel's for (S, nsplit) - per, the 16-wave decision, the partial-state
+// layout, the tickets, the reducer's order - and the key loop, the slot / wave merges and the reducer below are the statements of
+// attn_fused_decode_kernel, so every partial state and every y is the one parrot_attn_fused_decode_rows computes on B full caches
+// that each hold a copy of the prompt (tests/test_candidates_gpu.py compares the bits).  It is a kernel of its own and not two more
+// template switches of attn_fused_decode_kernel: with them the existing instantiations changed registers and occupancy.
+// Two launches per layer:
+//   KIND 2, first, only when q_per_kv <= 2, nsplit > 1 and B > 1: a workgroup takes the 4 / q_per_kv rows of one row block as
+//     "virtual query heads" of the group (HQ = 4) for a split with s_begin + per <= T, whose keys are the same for every row: it
+//     ropes row b's q at pos[b], loads each K/V row once, keeps one softmax state per (row, head), writes the rows' partial states
+//     and arrives once at each row's ticket.  Workgroups of other splits exit at once.  It never merges: the last split ends at
+//     S > pos[b] >= T and is never shared, so no ticket reaches nsplit here.
+//   KIND 1, second: the batched kernel's workgroup with the address translation.  Workgroups of the splits the first launch served
+//     exit without an arrival, so every ticket counts exactly nsplit arrivals and the last arriver of this launch merges.
+// T is clamped to [0, S], pos to [0, S-1] and the tail index to [0, S_tail-1]: no address leaves the buffers whatever they hold.
+struct AttnPrefixArgs {
+    int ldqkv, ldy;
+    bf16_t* k_tail;             // [B][n_groups][S_tail][hs]
+    bf16_t* v_tail;
+    const int32_t* prefix_len;  // T, on the device: one captured launch serves every prompt length
+    int S_tail, B, share;       // share: splits entirely below T belong to the KIND 2 launch
+};
+
+template <int HS, int HQ, int WAVES, bool PM, int KIND>
+__global__ void __launch_bounds__(WAVES * 64)
+attn_prefix_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restrict__ rope_cos, const __half* __restrict__ rope_sin,
+                          int n_elem, const int32_t* __restrict__ pos_ptr, const bf16_t* __restrict__ k_cache,
+                          const bf16_t* __restrict__ v_cache, int n_groups, int q_per_kv, int S, int nsplit, float* __restrict__ ws,
+                          unsigned int* __restrict__ tickets, bf16_t* __restrict__ y, AttnPrefixArgs pa) {
+    constexpr int LPR = HS / 8;
+    constexpr int RPW = 64 / LPR;
+    constexpr int STRIDE = WAVES * RPW;
+    constexpr int NQ = KIND == 2 ? HQ : kFusedMaxQ;  // roped q rows held in LDS
+    __shared__ float sh_acc[HQ][WAVES][HS];  // one merged state per wave
+    __shared__ float sh_m[HQ][WAVES], sh_l[HQ][WAVES];
+    __shared__ __attribute__((aligned(16))) bf16_t sh_q[NQ][HS];
+    __shared__ __attribute__((aligned(16))) bf16_t sh_kv[2][HS];  // roped k_new, v_new as stored in the tail (KIND 1)
+    __shared__ int sh_last;
+
+    const int n_head = n_groups * q_per_kv;
+    const int g = blockIdx.x, split = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LPR, dl = lane % LPR;
+    // KIND 1: blockIdx.z = row * nchunk + chunk of the group's query heads, as in the batched kernel
+    // KIND 2: blockIdx.z = block of R rows; virtual head t is query head t % q_per_kv of row rb * R + t / q_per_kv (one chunk)
+    const int nchunk = (q_per_kv + HQ - 1) / HQ;
+    const int b = KIND == 1 ? blockIdx.z / nchunk : 0;
+    const int chunk = KIND == 1 ? blockIdx.z - b * nchunk : 0;
+    const int rb = blockIdx.z, R = HQ / q_per_kv;
+    const int h0 = chunk * HQ;
+    const int T = min(max(pa.prefix_len[0], 0), S);
+    const int per = (S + nsplit - 1) / nsplit;
+    const int s_begin = split * per;
+    // every key of the split is a prompt key, the same for all rows (never the last split)
+    const bool shared = split < nsplit - 1 && s_begin + per <= T;
+    if (KIND == 2 ? !shared : (shared && pa.share != 0)) return;  // the other launch's split (workgroup-uniform, before any barrier)
+
+    const int pos = min(max(pos_ptr[b], 0), S - 1);
+    const int n_valid = pos + 1;
+    const int slot_new = KIND == 2 ? -1 : pos;  // (a shared split never holds a row's new slot)
+    const int s_end = KIND == 2 ? s_begin + per : min(n_valid, s_begin + per);
+    const float scale = 1.0f / sqrtf((float)HS);
+    const int half_n = n_elem >> 1;
+    const int tail_new = min(max(pos - T, 0), pa.S_tail - 1);  // KIND 1: where the new K/V row goes
+
+    const uint4* kc = reinterpret_cast<const uint4*>(k_cache + (int64_t)g * S * HS);
+    const uint4* vc = reinterpret_cast<const uint4*>(v_cache + (int64_t)g * S * HS);
+    const int64_t toff = ((int64_t)b * n_groups + g) * pa.S_tail * HS;
+    const uint4* kt = reinterpret_cast<const uint4*>(pa.k_tail + toff);
+    const uint4* vt = reinterpret_cast<const uint4*>(pa.v_tail + toff);
+    // this lane's 16 bytes of the K / V row of logical slot s: the base is picked per key, the load itself stays unconditional
+    auto ldk = [&](int s) -> uint4 {
+        if constexpr (KIND == 2) {
+            return kc[(int64_t)s * LPR + dl];
+        } else {
+            const bool low = s < T;
+            return (low ? kc : kt)[(int64_t)(low ? s : min(s - T, pa.S_tail - 1)) * LPR + dl];
+        }
+    };
+    auto ldv = [&](int s) -> uint4 {
+        if constexpr (KIND == 2) {
+            return vc[(int64_t)s * LPR + dl];
+        } else {
+            const bool low = s < T;
+            return (low ? vc : vt)[(int64_t)(low ? s : min(s - T, pa.S_tail - 1)) * LPR + dl];
+        }
+    };
+
+    // ---- load order as in attn_fused_decode_kernel: the RoPE operands, then this wave's first K/V rows, then the RoPE arithmetic
+    // (x*cos + rotate_half(x)*sin, each product and the sum rounded to fp32 separately; cos = 1, sin = 0 outside the rotary part)
+    constexpr int ROPE_IT = ((KIND == 2 ? HQ : kFusedMaxQ + 2) * HS + WAVES * 64 - 1) / (WAVES * 64);
+    const bf16_t* grp = qkv + (int64_t)b * pa.ldqkv + (int64_t)g * (q_per_kv + 2) * HS;
+    const int n_rope_elems = KIND == 2 ? HQ * HS : (q_per_kv + 2) * HS;  // KIND 2: the query heads of the R rows, no k / v
+    float rx[ROPE_IT], ro[ROPE_IT], rc[ROPE_IT], rs[ROPE_IT];
+#pragma unroll
+    for (int it = 0; it < ROPE_IT; ++it) {
+        const int idx = threadIdx.x + it * WAVES * 64;
+        rx[it] = ro[it] = rs[it] = 0.f;
+        rc[it] = 1.f;
+        if (idx < n_rope_elems) {
+            const int t = idx / HS, d = idx % HS;
+            const bf16_t* src = grp + idx;
+            int rpos = pos;
+            bool rotary = t <= q_per_kv;
+            if constexpr (KIND == 2) {
+                const int row = min(rb * R + t / q_per_kv, pa.B - 1);  // (a ragged block ropes the last row again and drops it)
+                src = grp + (int64_t)row * pa.ldqkv + (t % q_per_kv) * HS + d;
+                rpos = min(max(pos_ptr[row], 0), S - 1);
+                rotary = true;
+            }
+            rx[it] = bf2f(src[0]);
+            if (rotary && d < n_elem) {
+                rc[it] = __half2float(rope_cos[(int64_t)rpos * n_elem + d]);
+                rs[it] = __half2float(rope_sin[(int64_t)rpos * n_elem + d]);
+                ro[it] = d < half_n ? -bf2f(src[half_n]) : bf2f(src[-half_n]);
+            }
+        }
+    }
+    const int s_first = s_begin + wave * RPW;
+    const int s_last = max(s_end - 1, 0);
+    const int sc_first = min(s_first + sub, s_last);
+    const uint4 kv_cur = ldk(sc_first);
+    const uint4 vv_cur = ldv(sc_first);
+#pragma unroll
+    for (int it = 0; it < ROPE_IT; ++it) {
+        const int idx = threadIdx.x + it * WAVES * 64;
+        if (idx < n_rope_elems) {
+            const int t = idx / HS, d = idx % HS;
+            const float v = __fadd_rn(__fmul_rn(rx[it], rc[it]), __fmul_rn(ro[it], rs[it]));
+            const bf16_t vb = f2bf(v);
+            if (KIND == 2 || t < q_per_kv)
+                sh_q[t][d] = vb;
+            else
+                sh_kv[t - q_per_kv][d] = vb;
+        }
+    }
+    __syncthreads();
+    uint4 knew = kv_cur, vnew = vv_cur;  // (KIND 2: never used)
+    if constexpr (KIND == 1) {
+        // ---- KV append to the row's tail by the workgroup that owns the new slot
+        if (chunk == 0 && slot_new >= s_begin && slot_new < s_begin + per && threadIdx.x < 2 * LPR) {
+            const int which = threadIdx.x / LPR, c = threadIdx.x % LPR;
+            bf16_t* dst = (which ? pa.v_tail : pa.k_tail) + toff + (int64_t)tail_new * HS;
+            reinterpret_cast<uint4*>(dst)[c] = reinterpret_cast<const uint4*>(sh_kv[which])[c];
+        }
+        knew = reinterpret_cast<const uint4*>(sh_kv[0])[dl];
+        vnew = reinterpret_cast<const uint4*>(sh_kv[1])[dl];
+    }
+
+    {
+        uint32_t qp[HQ][4];  // this lane's 8 dims of every query head, packed bf16 pairs (operand of v_dot2_f32_bf16)
+        float mrun[HQ], lrun[HQ], acc[HQ][8];
+#pragma unroll
+        for (int hh = 0; hh < HQ; ++hh) {
+            const int hq = KIND == 2 ? hh : min(h0 + hh, q_per_kv - 1);
+            const uint4 qv = reinterpret_cast<const uint4*>(sh_q[hq])[dl];
+            qp[hh][0] = qv.x;
+            qp[hh][1] = qv.y;
+            qp[hh][2] = qv.z;
+            qp[hh][3] = qv.w;
+            mrun[hh] = -INFINITY;
+            lrun[hh] = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[hh][e] = 0.f;
+        }
+        float gmax[HQ];  // PM: the maximum score over all the keys of this head
+        if constexpr (PM) {
+#pragma unroll
+            for (int hh = 0; hh < HQ; ++hh) gmax[hh] = -INFINITY;
+            for (int s0 = s_first; s0 < s_end; s0 += STRIDE) {
+                const int sk = min(s0 + sub, s_last);
+                uint4 kv = ldk(sk);
+                if (sk == slot_new) kv = knew;  // the row being appended by this launch
+#pragma unroll
+                for (int hh = 0; hh < HQ; ++hh) {
+                    float p0 = dot2_bf16(kv.x, qp[hh][0], 0.f), p1 = dot2_bf16(kv.y, qp[hh][1], 0.f);
+                    p0 = dot2_bf16(kv.z, qp[hh][2], p0);
+                    p1 = dot2_bf16(kv.w, qp[hh][3], p1);
+                    const float sc_ = group_sum<LPR>(p0 + p1) * scale;
+                    if (s0 + sub < s_end) gmax[hh] = fmaxf(gmax[hh], sc_);
+                }
+            }
+#pragma unroll
+            for (int hh = 0; hh < HQ; ++hh) {
+                gmax[hh] = slot_allreduce<LPR, true>(gmax[hh]);
+                if (lane == 0) sh_m[hh][wave] = gmax[hh];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int hh = 0; hh < HQ; ++hh) {
+                for (int t = 0; t < WAVES; ++t) gmax[hh] = fmaxf(gmax[hh], sh_m[hh][t]);
+                mrun[hh] = gmax[hh];
+            }
+            __syncthreads();  // (sh_m is written again by the wave merge below)
+        }
+        // one step = the STRIDE keys of the workgroup; this lane: key s, dims 8*dl .. 8*dl+7
+        auto step = [&](uint4 kv, uint4 vv, int s) {
+            const bool ok = s < s_end;
+            if ((ok ? s : s_last) == slot_new) {  // the row being appended by this launch: use the in-register copy
+                kv = knew;
+                vv = vnew;
+            }
+            const uint32_t vd[4] = {vv.x, vv.y, vv.z, vv.w};
+            float vf[8];
+#pragma unroll
+            for (int jq = 0; jq < 4; ++jq) {
+                vf[2 * jq] = bflo(vd[jq]);
+                vf[2 * jq + 1] = bfhi(vd[jq]);
+            }
+#pragma unroll
+            for (int hh = 0; hh < HQ; ++hh) {
+                float p0 = dot2_bf16(kv.x, qp[hh][0], 0.f), p1 = dot2_bf16(kv.y, qp[hh][1], 0.f);
+                p0 = dot2_bf16(kv.z, qp[hh][2], p0);
+                p1 = dot2_bf16(kv.w, qp[hh][3], p1);
+                const float sc_ = ok ? group_sum<LPR>(p0 + p1) * scale : -INFINITY;  // a masked key never raises the maximum
+                if constexpr (PM) {
+                    const float p = ok ? expf(sc_ - gmax[hh]) : 0.f;
+                    const float pr = rbf(p);  // the probability as the reference's P.V product sees it
+                    lrun[hh] += p;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[hh][e] = fmaf(pr, vf[e], acc[hh][e]);
+                    continue;
+                }
+                const float mn = fmaxf(mrun[hh], sc_);
+                const float corr = (mn == -INFINITY) ? 1.f : __expf(mrun[hh] - mn);
+                const float p = (mn == -INFINITY) ? 0.f : __expf(sc_ - mn);
+                lrun[hh] = lrun[hh] * corr + p;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[hh][e] = acc[hh][e] * corr + p * vf[e];
+                mrun[hh] = mn;
+            }
+        };
+        // two register sets in ping-pong; every load is unconditional (rows past the range are clamped and masked in step())
+        uint4 k0 = kv_cur, v0 = vv_cur;
+        for (int s0 = s_first; s0 < s_end; s0 += 2 * STRIDE) {
+            const int sn1 = min(s0 + STRIDE + sub, s_last);
+            const uint4 k1 = ldk(sn1), v1 = ldv(sn1);
+            step(k0, v0, s0 + sub);
+            const int sn2 = min(s0 + 2 * STRIDE + sub, s_last);
+            k0 = ldk(sn2);
+            v0 = ldv(sn2);
+            if (s0 + STRIDE < s_end) step(k1, v1, s0 + STRIDE + sub);  // wave-uniform
+        }
+        // merge the RPW row slots of this wave, one state per wave to LDS
+#pragma unroll
+        for (int hh = 0; hh < HQ; ++hh) {
+            const float mw = slot_allreduce<LPR, true>(mrun[hh]);
+            const float c = (mrun[hh] == -INFINITY) ? 0.f : __expf(mrun[hh] - mw);
+            lrun[hh] = slot_allreduce<LPR, false>(lrun[hh] * c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[hh][e] = slot_allreduce<LPR, false>(acc[hh][e] * c);
+            mrun[hh] = mw;
+            if (sub == 0) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sh_acc[hh][wave][dl * 8 + e] = acc[hh][e];
+                if (dl == 0) {
+                    sh_m[hh][wave] = mrun[hh];
+                    sh_l[hh][wave] = lrun[hh];
+                }
+            }
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < HQ * HS; idx += WAVES * 64) {
+            const int hh = idx / HS, d = idx % HS;
+            const int row = KIND == 2 ? rb * R + hh / q_per_kv : b;  // KIND 2: the row of virtual head hh
+            if (KIND == 2 ? row < pa.B : h0 + hh < q_per_kv) {
+                constexpr int NSLOT = WAVES;
+                float mx = -INFINITY;
+                for (int t = 0; t < NSLOT; ++t) mx = fmaxf(mx, sh_m[hh][t]);
+                float l = 0.f, a = 0.f;
+                for (int t = 0; t < NSLOT; ++t) {
+                    const float mt = sh_m[hh][t];
+                    const float wgt = (mt == -INFINITY) ? 0.f : __expf(mt - mx);
+                    l += sh_l[hh][t] * wgt;
+                    a += sh_acc[hh][t][d] * wgt;
+                }
+                const int head = g * q_per_kv + (KIND == 2 ? hh % q_per_kv : h0 + hh);
+                if (nsplit == 1) {
+                    y[(int64_t)row * pa.ldy + (int64_t)head * HS + d] = f2bf(a / l);
+                } else {
+                    float* p = ws + (((int64_t)row * n_head + head) * nsplit + split) * (HS + 2);
+                    store_agent(p + d, a);
+                    if (d == 0) {
+                        store_agent(p + HS, mx);
+                        store_agent(p + HS + 1, l);
+                    }
+                }
+            }
+        }
+    }
+    if (nsplit == 1) return;
+    // ---- arrival tickets (they only count; nobody waits): the last workgroup of a (row, group, chunk) merges the splits
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores
+    __syncthreads();
+    if constexpr (KIND == 2) {  // one arrival per served row; the merge is the per-row launch's
+        if ((int)threadIdx.x < R && rb * R + (int)threadIdx.x < pa.B)
+            __hip_atomic_fetch_add(&tickets[(rb * R + threadIdx.x) * n_head + g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    unsigned int* ticket = &tickets[b * n_head + g * nchunk + chunk];
+    if (threadIdx.x == 0) {
+        const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sh_last = (t == (unsigned int)(nsplit - 1));
+        if (sh_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+    }
+    __syncthreads();
+    if (!sh_last) return;
+    for (int idx = threadIdx.x; idx < HQ * HS; idx += WAVES * 64) {
+        const int hq = h0 + idx / HS, d = idx % HS;
+        if (hq >= q_per_kv) continue;
+        const int head = g * q_per_kv + hq;
+        const float* p = ws + ((int64_t)b * n_head + head) * nsplit * (HS + 2);
+        float mx = -INFINITY;
+        for (int t = 0; t < nsplit; ++t) mx = fmaxf(mx, load_agent(p + t * (HS + 2) + HS));
+        float l = 0.f, a = 0.f;
+        for (int t = 0; t < nsplit; ++t) {
+            const float mt = load_agent(p + t * (HS + 2) + HS);
+            const float wgt = (mt == -INFINITY) ? 0.f : __expf(mt - mx);
+            l += load_agent(p + t * (HS + 2) + HS + 1) * wgt;
+            a += load_agent(p + t * (HS + 2) + d) * wgt;
+        }
+        y[(int64_t)b * pa.ldy + (int64_t)head * HS + d] = f2bf(a / l);
+    }
+}
+
+// both launches of one layer (see above); the per-row launch always runs
+template <int HS>
+static int attn_prefix_launch(const void* qkv, const void* cosp, const void* sinp, int n_elem, const int32_t* pos, const void* k_cache,
+                              const void* v_cache, int n_groups, int q_per_kv, int S, int nsplit, void* ws, void* tickets, void* y,
+                              int softmax_mode, hipStream_t st, int B, AttnPrefixArgs pa) {
+    const int hq = q_per_kv == 1 ? 1 : (q_per_kv == 2 ? 2 : 4);
+    const int per = (S + nsplit - 1) / nsplit;
+    const bool wide = per > 2 * kAttnWaves * (64 / (HS / 8));  // the rows kernel's decision
+#define PARROT_PREFIX_GO(HQV, WV, PMV, KINDV, GRID)                                                                                      \
+    launch(K_ATTN_FUSED_PREFIX, attn_prefix_decode_kernel<HS, HQV, WV, PMV, KINDV>, GRID, dim3(WV * 64), 0, st, (const bf16_t*)qkv,        \
+           (const __half*)cosp, (const __half*)sinp, n_elem, pos, (const bf16_t*)k_cache, (const bf16_t*)v_cache, n_groups, q_per_kv, S,  \
+           nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, pa)
+    pa.share = pa.share != 0 && nsplit > 1 && q_per_kv <= 2 && B > 1;
+    if (pa.share) {
+        const int R = 4 / q_per_kv;
+        const dim3 grid2(n_groups, nsplit - 1, (B + R - 1) / R);  // (the last split is never shared)
+        const int rc = wide ? PARROT_PREFIX_GO(4, 16, false, 2, grid2) : PARROT_PREFIX_GO(4, kAttnWaves, false, 2, grid2);
+        if (rc != PARROT_OK) return rc;
+    }
+    const dim3 grid(n_groups, nsplit, B * ((q_per_kv + hq - 1) / hq));
+    if (softmax_mode == 1) {
+        if (q_per_kv == 1) return PARROT_PREFIX_GO(1, 16, true, 1, grid);
+        if (q_per_kv == 2) return PARROT_PREFIX_GO(2, 16, true, 1, grid);
+        return PARROT_PREFIX_GO(4, 16, true, 1, grid);
+    }
+    if (wide) {
+        if (q_per_kv == 1) return PARROT_PREFIX_GO(1, 16, false, 1, grid);
+        if (q_per_kv == 2) return PARROT_PREFIX_GO(2, 16, false, 1, grid);
+        return PARROT_PREFIX_GO(4, 16, false, 1, grid);
+    }
+    if (q_per_kv == 1) return PARROT_PREFIX_GO(1, kAttnWaves, false, 1, grid);
+    if (q_per_kv == 2) return PARROT_PREFIX_GO(2, kAttnWaves, false, 1, grid);
+    return PARROT_PREFIX_GO(4, kAttnWaves, false, 1, grid);
+#undef PARROT_PREFIX_GO
+}
+
 }  // namespace parrot
 
 using namespace parrot;
@@ -1012,6 +1375,42 @@ int parrot_attn_fused_decode_seq(const void* qkv, int ldqkv, int M, const void* 
                                  void* stream) {
     return attn_fused_rows_entry<true>("attn_fused_decode_seq", qkv, ldqkv, M, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S,
                                        nsplit, workspace, tickets, n_tickets, k_cache, v_cache, 0, y, ldy, softmax_mode, stream);
+}
+
+int parrot_attn_fused_decode_prefix(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                    const int32_t* pos, const int32_t* prefix_len, int n_groups, int q_per_kv, int hs, int S, int nsplit,
+                                    void* workspace, void* tickets, int n_tickets, const void* k_cache, const void* v_cache, void* k_tail,
+                                    void* v_tail, int S_tail, void* y, int ldy, int share_loads, int softmax_mode, void* stream) {
+    const char* who = "attn_fused_decode_prefix";
+    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "%s: B=%d (1 .. %d)", who, B, kMaxDecodeRows);
+    {
+        const int rc = check_softmax_mode(who, softmax_mode, S, nsplit);
+        if (rc != PARROT_OK) return rc;
+    }
+    PARROT_REQUIRE(qkv && pos && prefix_len && k_cache && v_cache && k_tail && v_tail && y, "%s: null pointer", who);
+    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1 && S_tail >= 1, "%s: bad shape (S=%d S_tail=%d)", who, S, S_tail);
+    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "%s: at most %d query heads per group (got %d)", who, kFusedMaxQ, q_per_kv);
+    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
+    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "%s: bad n_elem=%d", who, n_elem);
+    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "%s: rope tables missing", who);
+    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "%s: nsplit out of range", who);
+    const int n_head = n_groups * q_per_kv;
+    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "%s: workspace and tickets required when nsplit > 1", who);
+    PARROT_REQUIRE(!tickets || n_tickets >= B * n_head, "%s: %d tickets, B * n_head = %d needed", who, n_tickets, B * n_head);
+    PARROT_REQUIRE(ldqkv >= n_groups * (q_per_kv + 2) * hs && ldqkv % 8 == 0, "%s: ldqkv=%d too small or not a multiple of 8", who, ldqkv);
+    PARROT_REQUIRE(ldy >= n_head * hs, "%s: ldy=%d too small", who, ldy);
+    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache) && aligned16(k_tail) && aligned16(v_tail),
+                   "%s: 16-byte alignment", who);
+    const AttnPrefixArgs pa{ldqkv, ldy, (bf16_t*)k_tail, (bf16_t*)v_tail, prefix_len, S_tail, B, share_loads};
+    hipStream_t st = (hipStream_t)stream;
+    switch (hs) {
+        case 32: return attn_prefix_launch<32>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace,
+                                               tickets, y, softmax_mode, st, B, pa);
+        case 64: return attn_prefix_launch<64>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace,
+                                               tickets, y, softmax_mode, st, B, pa);
+        default: return attn_prefix_launch<128>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace,
+                                                tickets, y, softmax_mode, st, B, pa);
+    }
 }
 
 // prefix K/V, gate and aT of the two adapter entry points

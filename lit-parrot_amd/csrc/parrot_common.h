@@ -105,6 +105,7 @@ enum KernelId : int {
     K_ATTN_FUSED_SEQ,
     K_NGRAM_DRAFT,
     K_VERIFY_ADVANCE,
+    K_ATTN_FUSED_PREFIX,
     K_COUNT
 };
 

@@ -419,6 +419,191 @@ def generate_batch(
     return out
 
 
+# ------------------------------------------------------------------------------------------------ candidates of one prompt
+TAIL_BUCKET = 64  # a candidate's own cache holds the generated tokens only, rounded up to this many slots
+
+
+def candidate_tail_slots(max_returned_tokens: int, T: int) -> int:
+    """Slots of a candidate's tail cache: ``max_returned_tokens - T`` rounded up to a multiple of TAIL_BUCKET (the session key)."""
+    return -(-(max_returned_tokens - T) // TAIL_BUCKET) * TAIL_BUCKET
+
+
+def shared_splits(S: int, nsplit: int, T: int) -> List[int]:
+    """The splits of a window of ``S`` slots in ``nsplit`` parts whose keys all lie inside a prompt of ``T`` tokens: the same for
+    every candidate, so the attention serves them with workgroups that load each K/V row once for several rows
+    (csrc/attn.hip, attn_prefix_decode_kernel).  ``per = ceil(S / nsplit)``; split j is shared when ``(j + 1) * per <= T``; never
+    the last one, which ends at S > pos >= T."""
+    per = -(-S // nsplit)
+    T = min(max(T, 0), S)
+    return [j for j in range(nsplit - 1) if (j + 1) * per <= T]
+
+
+def ticket_arrivals(S: int, nsplit: int, T: int, share: bool = True) -> Tuple[int, int]:
+    """Arrivals at one (row, group, chunk) ticket from the shared-load launch and from the per-row launch: together always
+    ``nsplit``, and the per-row launch, which merges, always makes the last one."""
+    n = len(shared_splits(S, nsplit, T)) if share and nsplit > 1 else 0
+    return n, nsplit - n
+
+
+class CandidateSession(BatchDecodeSession):
+    """Static buffers + captured graph of the candidates step: n rows (1 <= n <= 8) that continue ONE prompt.
+
+        tokens      int64[n][L]   every row: the prompt, then the row's sampled tokens
+        pos, end    int32[n]      as in BatchDecodeSession
+        prefix_len  int32[1]      the prompt length T, on the device: one captured step serves every prompt whose tail fits
+        caches      the model's batch-1 ``kv_caches`` (n_groups, S, hs): the prompt at slots 0 .. T-1, prefilled ONCE
+        tails       (n, n_groups, S_tail, hs) per layer, K and V: row b's position p >= T at ``tail[b][:, p - T]``
+
+    The step is BatchDecodeSession's with ``ops.attn_fused_decode_prefix`` as the attention, which computes every row bit for bit
+    as ``attn_fused_decode_rows`` does on n full caches that each hold a copy of the prompt: ``generate_candidates`` returns
+    ``generate_batch(model, [idx] * n, ...)``'s tokens with one prefill and one copy of the prompt K/V.  Positions address both
+    caches directly, so the window must hold every position (no ring wrap)."""
+
+    def __init__(self, model: GPT, n: int, max_seq_length: int, tail_slots: int, greedy: bool,
+                 sampler: Optional[Tuple[float, Optional[int]]] = None, eos_id: int = -1, use_graph: bool = True) -> None:
+        self.model, self.B, self.S, self.greedy, self.eos_id = model, n, max_seq_length, greedy, eos_id
+        self.S_tail = tail_slots
+        self.sampler = None if greedy else sampler
+        dev = model.transformer.wte.weight.device
+        if dev.type != "cuda":
+            raise ParrotHipError("generate_candidates() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+        self.device = dev
+        c = model.config
+        self.tokens = torch.zeros((n, max_seq_length + 1), dtype=torch.int64, device=dev)  # (no position reaches the window's end)
+        self.pos = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.end = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.prefix_len = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.ws = model.workspace(n, dev, n, rows_share_prefix=True)
+        V = c.padded_vocab_size
+        self.first_logits = torch.empty((n, V), dtype=torch.bfloat16, device=dev)
+        self.noise = torch.empty((n, V), dtype=torch.bfloat16, device=dev) if self.sampler is not None else None
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.use_graph = use_graph
+        if model.rope_cache is None:
+            model.rope_cache = model.build_rope_cache(self.tokens)
+        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != 1:
+            model.kv_caches = model.build_kv_caches(self.tokens[:1], max_seq_length, model.rope_cache[0].size(-1))
+        self.caches = [(k[0], v[0]) for k, v in model.kv_caches]  # the shared prompt cache: (n_groups, S, hs) per layer
+        shape = (n, c.n_query_groups, tail_slots, c.head_size)
+        self.tails = [(torch.zeros(shape, dtype=torch.bfloat16, device=dev), torch.zeros(shape, dtype=torch.bfloat16, device=dev))
+                      for _ in range(c.n_layer)]
+        self.prefix_caches = [(ops.PrefixCache(k, tk, self.prefix_len), ops.PrefixCache(v, tv, self.prefix_len))
+                              for (k, v), (tk, tv) in zip(self.caches, self.tails)]
+        if RELEASE_REFERENCE_BUFFERS:
+            for m in model.modules():
+                if hasattr(m, "release_reference"):
+                    m.release_reference()
+
+    def kv_bytes(self) -> int:
+        """Bytes of K/V this session holds: the shared cache once and the n tails."""
+        return sum(t.numel() * t.element_size() for pair in self.caches + self.tails for t in pair)
+
+    def _step(self) -> None:
+        logits = self.model.run_rows(self.ws, self.tokens, self.pos, self.pos, self.S, self.prefix_caches, self.model.rope_cache)
+        self.sample(logits, self.eos_id)
+
+    def prefill(self, prompt: torch.Tensor, max_returned_tokens: int) -> None:
+        """The prompt ONCE through the multi-row path into the shared cache (DecodeSession.prefill); every row starts from its last
+        row's logits at pos = T - 1."""
+        T = prompt.numel()
+        self.tokens[:, :T] = prompt
+        ws = self.model.workspace(T, self.device, 1)
+        ws.pos_is_zero = True  # the prompt starts at position 0 (see DecodeSession.prefill)
+        try:
+            logits = self.model.run_rows(ws, self.tokens[0], None, self.zero_pos, self.S, self.caches, self.model.rope_cache)
+        finally:
+            ws.pos_is_zero = False
+        self.first_logits.copy_(logits[:1].expand(self.B, -1))
+        self.pos.fill_(T - 1)
+        self.end.fill_(max_returned_tokens)
+        self.prefix_len.fill_(T)
+
+    def capture(self) -> None:
+        if self.graph is not None or not self.use_graph:
+            return
+        # warm-up outside capture, restoring the loop state afterwards (as BatchDecodeSession.capture).  The step writes tokens, pos
+        # and tail slots only; a tail slot is always written by its own step before a later step reads it, so the tails need no restore
+        saved = (self.tokens.clone(), self.pos.clone())
+        rng = torch.cuda.get_rng_state(self.device) if self.sampler is not None else None
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            self._step()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._step()
+        self.graph = graph
+        if rng is not None:
+            torch.cuda.set_rng_state(rng, self.device)
+        self.tokens.copy_(saved[0])
+        self.pos.copy_(saved[1])
+
+
+@torch.no_grad()
+def generate_candidates(
+    model: torch.nn.Module,
+    idx: torch.Tensor,
+    n: int,
+    max_returned_tokens: int,
+    max_seq_length: int,
+    *,
+    temperature: float = 1.0,
+    top_k: Optional[int] = None,
+    eos_id: Optional[int] = None,
+) -> List[torch.Tensor]:
+    """``n`` samples of ONE prompt (the reference scripts' ``for _ in range(return_candidates): generate(...)``): exactly the tokens
+    of ``generate_batch(model, [idx] * n, max_returned_tokens, max_seq_length, ...)`` under the same torch seed - row b draws from
+    its own noise row, greedy rows equal ``generate()`` - with the prompt prefilled once and its K/V stored once: all rows attend to
+    the one shared prompt cache and each keeps a short cache of its own for the tokens it generates (CandidateSession)."""
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 1 or idx.numel() == 0:
+        raise ParrotHipError("generate_candidates: the prompt must be a non-empty 1-D token tensor")
+    if not isinstance(model, GPT):
+        raise ParrotHipError("generate_candidates() drives lit_parrot_amd.GPT models")
+    T = idx.numel()
+    assert max_returned_tokens > T  # generate()'s checks
+    assert max_seq_length <= model.config.block_size
+    if max_returned_tokens > model.config.block_size:
+        raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
+                             "positions past the RoPE tables")
+    assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
+    if not isinstance(n, int) or not 1 <= n <= ops.GEMV_MAX_ROWS:
+        raise ParrotHipError(f"generate_candidates: n={n}; the candidates step takes 1 to {ops.GEMV_MAX_ROWS} rows")
+    why = model.batched_decode_unsupported()
+    if why is not None:
+        raise ParrotHipError(f"generate_candidates: {why}; use generate() per candidate")
+    if max_seq_length < max_returned_tokens:
+        raise ParrotHipError(f"generate_candidates: max_seq_length={max_seq_length} < max_returned_tokens={max_returned_tokens}: the shared "
+                             "prompt cache and the candidates' own caches are addressed by position (no sliding window); use "
+                             "generate_batch(model, [idx] * n, ...)")
+    if model.transformer.wte.weight.device.type != "cuda":
+        raise ParrotHipError("generate_candidates() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    greedy = top_k == 1 and temperature > 0
+    sampler = None if greedy else (float(temperature), top_k)
+    eos = -1 if eos_id is None else int(eos_id)
+    tail = candidate_tail_slots(max_returned_tokens, T)
+    # (a captured step keeps the attention launches it was captured with: the switch is part of the key)
+    key = ("candidates", n, max_seq_length, tail, greedy, sampler, eos, bool(ops.CANDIDATES_SHARE_LOADS))
+    sess = _cached_session(model, key, max_returned_tokens, lambda: CandidateSession(model, n, max_seq_length, tail, greedy, sampler, eos))
+    sess.prefill(idx.to(device=sess.device, dtype=torch.int64), max_returned_tokens)
+    sess.capture()
+    sess.sample(sess.first_logits, -1)  # the first token of every row is drawn whatever the prompt's last token is
+    for _ in range(max_returned_tokens - T - 1):
+        if eos_id is not None and sess.all_frozen():  # host sync, as in generate()
+            break
+        sess.step()
+    tokens, pos = sess.tokens.cpu(), sess.pos.cpu()
+    out = []
+    for b in range(n):
+        m = int(pos[b]) + 1
+        if eos_id is not None and m > T and int(tokens[b, m - 1]) == eos:
+            m -= 1  # the reference returns idx[:input_pos]: the eos token is not part of the result
+        out.append(sess.tokens[b, :m].to(idx.dtype).clone())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ speculative decode
 class SpeculativeSession:
     """Greedy decoding of ONE sequence that verifies ``draft_len`` guessed tokens per weight pass (prompt-lookup speculative

@@ -54,15 +54,20 @@ class Workspace:
     position ``pos + b`` of one sequence.
     ``rows_are_drafts``: speculative decode - the rows are positions ``pos .. pos + M - 1`` of one sequence, as in a prompt, but
     every row must come out bit for bit as the one-row step computes it: its attention is the fused decode kernel's
-    (``ops.attn_fused_decode_seq``), not the prompt kernels'."""
+    (``ops.attn_fused_decode_seq``), not the prompt kernels'.
+    ``rows_share_prefix`` (implies ``rows_are_sequences``): candidates - the rows continue ONE prompt; the caches handed to
+    ``run_rows`` are ``ops.PrefixCache`` pairs (the prompt's K/V once, a tail per row) and the attention is
+    ``ops.attn_fused_decode_prefix``."""
 
     def __init__(self, config: Config, M: int, device, lm_rows: int, rows_are_sequences: bool = False,
-                 rows_are_drafts: bool = False) -> None:
+                 rows_are_drafts: bool = False, rows_share_prefix: bool = False) -> None:
         def buf(cols: int, rows: int = M) -> torch.Tensor:
             return torch.empty((rows, cols), dtype=torch.bfloat16, device=device)
 
         c = config
+        rows_are_sequences = rows_are_sequences or rows_share_prefix
         self.M, self.lm_rows, self.rows_are_sequences, self.rows_are_drafts = M, lm_rows, rows_are_sequences, rows_are_drafts
+        self.rows_share_prefix = rows_share_prefix
         self.x, self.t = buf(c.n_embd), buf(c.n_embd)
         self.qkv = buf(c.qkv_size)
         self.q = buf(c.n_head * c.head_size)
@@ -208,13 +213,15 @@ class GPT(nn.Module):
         ]
 
     def workspace(self, M: int, device, lm_rows: Optional[int] = None, rows_are_sequences: bool = False,
-                  rows_are_drafts: bool = False) -> Workspace:
+                  rows_are_drafts: bool = False, rows_share_prefix: bool = False) -> Workspace:
         lm_rows = M if lm_rows is None else lm_rows
-        key = (M, lm_rows, str(device)) + (("rows",) if rows_are_sequences else ()) + (("drafts",) if rows_are_drafts else ())
+        rows_are_sequences = rows_are_sequences or rows_share_prefix
+        key = ((M, lm_rows, str(device)) + (("rows",) if rows_are_sequences else ()) + (("drafts",) if rows_are_drafts else ())
+               + (("prefix",) if rows_share_prefix else ()))
         if key not in self._workspaces:
             if len(self._workspaces) > 8:
                 self._workspaces.clear()
-            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows_are_sequences, rows_are_drafts)
+            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows_are_sequences, rows_are_drafts, rows_share_prefix)
         return self._workspaces[key]
 
     def batched_decode_unsupported(self) -> Optional[str]:
@@ -259,7 +266,8 @@ class GPT(nn.Module):
         ``pos`` (device int32[1]) is the position of row 0; ``caches[i]`` are (n_groups, S, hs) views.  Returns
         ``ws.logits``: all rows, or only the last row when the workspace was built with ``lm_rows == 1``.
         Batched decode (``ws.rows_are_sequences``): row b embeds ``tokens[b, tok_pos[b]]`` (``tokens[b, 0]`` without tok_pos)
-        at position ``pos[b]`` (int32[M]); ``caches[i]`` are the (M, n_groups, S, hs) caches of the M sequences.
+        at position ``pos[b]`` (int32[M]); ``caches[i]`` are the (M, n_groups, S, hs) caches of the M sequences, or, with
+        ``ws.rows_share_prefix``, the ``ops.PrefixCache`` pair of the layer (``S`` is the shared cache's window).
         Speculative decode (``ws.rows_are_drafts``): the arguments of a prompt; the caller keeps ``pos + M`` inside the window.
         """
         M = ws.M
@@ -418,6 +426,9 @@ class CausalSelfAttention(nn.Module):
         if ws.rows_are_sequences:  # batched decode: one row per sequence, every row in one launch
             if prefix is not None:
                 raise ParrotHipError("the batched decode step has no adapter-prefix term: adapter models decode one sequence at a time")
+            if ws.rows_share_prefix:  # candidates: one shared prompt cache, a tail per row
+                return ops.attn_fused_decode_prefix(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,
+                                                    c.q_per_kv, c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
             return ops.attn_fused_decode_rows(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv,
                                               c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
         if ws.rows_are_drafts:  # speculative decode: append the K/V rows of all rows, then every row through the fused decode kernel

@@ -6,7 +6,7 @@ torch implementation.  Activations are bf16 rows ``(M, features)`` of ONE sequen
 """
 import ctypes as C
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -414,6 +414,51 @@ def attn_fused_decode_rows(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
                                                     hs, S, nsplit, ptr(workspace), ptr(tickets), tickets.numel(), ptr(k_cache),
                                                     ptr(v_cache), k_cache.stride(0), ptr(y), y.stride(0), ATTN_SOFTMAX_MODE, stream()),
           "parrot_attn_fused_decode_rows")
+    return y
+
+
+# generate_candidates: True sends the splits of the window that lie entirely inside the shared prompt to workgroups that load every
+# K/V row once for 4 / q_per_kv rows (q_per_kv <= 2); False: every row walks them itself.  The same bits either way (tests compare).
+# Off by default: measured (tools/candidates_bench.py) the shared loads win at 8 rows behind a 3072-token prompt
+# (step 1.20x against 1.14x of generate_batch's on Llama-2-7B int4) and lose at 2 and 4 rows, where the launch in front costs more
+CANDIDATES_SHARE_LOADS = False
+
+
+class PrefixCache(NamedTuple):
+    """One of K / V of one layer for rows that continue the same prompt: ``shared`` (n_groups, S, hs) holds the prompt at slots
+    0 .. T-1, ``tail`` (B, n_groups, S_tail, hs) row b's position p >= T at ``tail[b][:, p - T]``, ``prefix_len`` int32[1] = T."""
+    shared: torch.Tensor
+    tail: torch.Tensor
+    prefix_len: torch.Tensor
+
+
+def attn_fused_decode_prefix(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_elem: int, pos: torch.Tensor,
+                             k_cache: PrefixCache, v_cache: PrefixCache, n_groups: int, q_per_kv: int, hs: int, S: int,
+                             nsplit: int, workspace: torch.Tensor, tickets: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Candidates: row b of ``qkv`` is the new token of candidate b at position ``pos[b]`` >= T; it attends to the one shared
+    prompt cache and to its own tail, and its K/V row is appended to the tail.  Bit for bit ``attn_fused_decode_rows`` on B full
+    caches that each hold a copy of the prompt.  The caller keeps ``pos[b] < S`` and ``pos[b] - T < S_tail`` (no ring)."""
+    _rows(qkv, "attn_fused_decode_prefix"), _rows(y, "attn_fused_decode_prefix")
+    B = qkv.shape[0]
+    if pos.dtype != torch.int32 or pos.numel() != B or not pos.is_contiguous():
+        raise ParrotHipError("attn_fused_decode_prefix: pos must be a contiguous int32 vector of one position per row")
+    T = k_cache.prefix_len
+    if T.dtype != torch.int32 or T.numel() != 1 or v_cache.prefix_len.data_ptr() != T.data_ptr():
+        raise ParrotHipError("attn_fused_decode_prefix: prefix_len must be one int32[1] for K and V")
+    for c in (k_cache, v_cache):
+        if c.shared.dtype != torch.bfloat16 or tuple(c.shared.shape) != (n_groups, S, hs) or not c.shared.is_contiguous():
+            raise ParrotHipError(f"attn_fused_decode_prefix: the shared cache must be contiguous bf16 (n_groups, S, hs), got {tuple(c.shared.shape)}")
+        if (c.tail.dtype != torch.bfloat16 or c.tail.dim() != 4 or c.tail.shape[0] < B or c.tail.shape[1] != n_groups or c.tail.shape[2] < 1
+                or c.tail.shape[3] != hs or not c.tail.is_contiguous()):
+            raise ParrotHipError(f"attn_fused_decode_prefix: tails must be contiguous bf16 (B, n_groups, S_tail, hs), got {tuple(c.tail.shape)}")
+    if k_cache.tail.shape != v_cache.tail.shape or y.shape[0] != B or tickets.dtype != torch.int32:
+        raise ParrotHipError("attn_fused_decode_prefix: K / V tails of one shape, y (B, n_head * hs), int32 tickets expected")
+    check(_hip.load().parrot_attn_fused_decode_prefix(ptr(qkv), qkv.stride(0), B, ptr(cos), ptr(sin), n_elem, ptr(pos), ptr(T), n_groups,
+                                                      q_per_kv, hs, S, nsplit, ptr(workspace), ptr(tickets), tickets.numel(),
+                                                      ptr(k_cache.shared), ptr(v_cache.shared), ptr(k_cache.tail), ptr(v_cache.tail),
+                                                      k_cache.tail.shape[2], ptr(y), y.stride(0), int(CANDIDATES_SHARE_LOADS),
+                                                      ATTN_SOFTMAX_MODE, stream()),
+          "parrot_attn_fused_decode_prefix")
     return y
 
 
