@@ -20,6 +20,8 @@ draws the same tokens as those ops do on this device (tests/test_model_gpu.py::t
 The prompt is prefilled in one multi-row pass (same kernels, M = T rows) that computes only the last row of lm_head
 (the reference computes all T rows and discards T-1 of them, :135-136).
 """
+import contextlib
+import gc
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -27,6 +29,23 @@ import torch
 from .. import ops
 from .._hip import ParrotHipError
 from ..model import GPT
+
+
+@contextlib.contextmanager
+def _capturing(graph: "torch.cuda.CUDAGraph"):
+    """``torch.cuda.graph(graph)`` with Python's cyclic garbage collector out of the way.  A model and its cached sessions refer
+    to each other (``model._decode_sessions`` <-> ``session.model``), so a dropped model leaves its captured graphs and their memory
+    pools to the collector; a collection that falls INSIDE a capture destroys them there, which the runtime answers with an error
+    in a destructor: the process aborts.  (torch no longer collects on entering ``torch.cuda.graph``.)  The collector stays off
+    until the capture has ended; the dead cycles go with the next regular collection."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class DecodeSession:
@@ -123,7 +142,7 @@ class DecodeSession:
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with _capturing(graph):
             self._step()
         self.graph = graph
         if rng is not None:
@@ -325,7 +344,7 @@ class BatchDecodeSession:
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with _capturing(graph):
             self._step()
         self.graph = graph
         if rng is not None:
@@ -533,7 +552,7 @@ class CandidateSession(BatchDecodeSession):
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with _capturing(graph):
             self._step()
         self.graph = graph
         if rng is not None:
@@ -721,7 +740,7 @@ class SpeculativeSession:
             torch.cuda.synchronize(self.device)
             restore()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with _capturing(graph):
                 step()
             self.graphs[is_rows] = graph
             restore()

@@ -15,6 +15,8 @@ from .config import Config
 
 def synthetic_state_dict(config: Config, seed: int = 1234, *, dtype: torch.dtype = torch.float32, device="cpu",
                          perturb: bool = False) -> Dict[str, torch.Tensor]:
+    """Random weights make attention near-uniform (the logits barely depend on which keys were read): retrieval behaviour is
+    tested with the hand-built model of tests/retrieval_model.py."""
     gen = torch.Generator(device=device).manual_seed(seed)
     c = config
 
