@@ -48,28 +48,119 @@ def _capturing(graph: "torch.cuda.CUDAGraph"):
             gc.enable()
 
 
-class DecodeSession:
+# ------------------------------------------------------------------------------------------------ what every session shares
+def _check_args(fn: str, model: torch.nn.Module, lengths: Sequence[int], max_returned_tokens: int, max_seq_length: int,
+                length_first: bool = False) -> None:
+    """The model class and generate()'s checks (reference generate/base.py:118-127) for a prompt of each of ``lengths`` tokens.
+    ``length_first``: generate()'s own order, whose first assert - the reference's first line - comes before the model's class."""
+    if length_first:
+        assert max_returned_tokens > lengths[0]
+    if not isinstance(model, GPT):
+        raise ParrotHipError(f"{fn}() drives lit_parrot_amd.GPT models")
+    block_size = model.config.block_size
+    for T in lengths:
+        assert max_returned_tokens > T
+        assert max_seq_length <= block_size
+        if max_returned_tokens > block_size:
+            # positions index the RoPE tables (block_size rows); the reference fails at rope.index_select in this case
+            # (lit_gpt/model.py:88) - here the kernels would read past the tables on the device
+            raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={block_size}: "
+                                 "positions past the RoPE tables")
+        assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
+
+
+def _cuda_device(fn: str, model: GPT) -> torch.device:
+    dev = model.transformer.wte.weight.device
+    if dev.type != "cuda":
+        raise ParrotHipError(f"{fn}() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    return dev
+
+
+def _run_prompt(model: GPT, tokens: torch.Tensor, T: int, zero_pos: torch.Tensor, S: int, caches: List) -> torch.Tensor:
+    """``tokens[:T]`` through the multi-row path (M = T rows) into ``caches`` (one ``(k, v)`` of (n_groups, S, hs) per layer);
+    returns the last row's logits (1, V).  ``zero_pos``: an int32[1] on the device that holds 0."""
+    ws = model.workspace(T, tokens.device, 1)
+    ws.pos_is_zero = True  # the prompt starts at position 0: its attention may take the MFMA kernel (no ring wrap in the call)
+    try:
+        return model.run_rows(ws, tokens, None, zero_pos, S, caches, model.rope_cache)
+    finally:
+        ws.pos_is_zero = False
+
+
+def _capture(step: Callable[[], object], written: Sequence[torch.Tensor], device: torch.device, draws_rng: bool) -> "torch.cuda.CUDAGraph":
+    """The graph of ``step()``: warmed up outside the capture on a side stream (lazy W4K repacks, workspace allocations), then
+    captured.  ``written`` names the loop state the step writes; it is put back after the warm-up and after the capture (which
+    only records the launches), so the caller's state is what it was.  A sampling step (``draws_rng``) draws from torch's
+    generator: its state is put back too, so the warm-up does not use up draws of the caller's seed."""
+    kept = [t.clone() for t in written]
+    rng = torch.cuda.get_rng_state(device) if draws_rng else None
+
+    def restore() -> None:
+        for t, t0 in zip(written, kept):
+            t.copy_(t0)
+
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        step()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    restore()
+    graph = torch.cuda.CUDAGraph()
+    with _capturing(graph):
+        step()
+    restore()
+    if rng is not None:
+        torch.cuda.set_rng_state(rng, device)
+    return graph
+
+
+class _Session:
+    """The construction and the capture the four sessions share.  A session adds its buffers, ``_step`` (the launch sequence that
+    gets captured) and, where the step writes something else than tokens, pos and the K/V caches, ``_written``."""
+
+    def _open(self, fn: str, model: GPT, max_seq_length: int, tokens_shape: Tuple[int, ...], kv_batch: int, use_graph: bool) -> None:
+        """The device (``fn``: the entry point an error names), the token buffer, the model's RoPE tables and its ``kv_caches``
+        with batch ``kv_batch`` and a window of ``max_seq_length`` slots, rebuilt when they are anything else."""
+        self.model, self.S, self.use_graph = model, max_seq_length, use_graph
+        self.device = _cuda_device(fn, model)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.tokens = torch.zeros(tokens_shape, dtype=torch.int64, device=self.device)
+        if model.rope_cache is None:
+            model.rope_cache = model.build_rope_cache(self.tokens)
+        kv = model.kv_caches
+        if not kv or kv[0][0].size(2) != max_seq_length or kv[0][0].size(0) != kv_batch:
+            model.kv_caches = model.build_kv_caches(self.tokens.new_empty((kv_batch, 0)), max_seq_length, model.rope_cache[0].size(-1))
+
+    def _drop_reference_weights(self) -> None:
+        """One resident image of the int4 weights: W4K (the multi-launch step's and every prompt's format; the engine keeps
+        its E4 copy beside it).  The reference-layout buffers are released; state_dict() / get_weight() rebuild them exactly."""
+        if RELEASE_REFERENCE_BUFFERS:
+            for m in self.model.modules():
+                release = getattr(m, "release_reference", None)
+                if release is not None:
+                    release()
+
+    def _written(self) -> List[torch.Tensor]:
+        return [self.tokens, self.pos] + [t for kv in self.caches for t in kv]
+
+    def capture(self) -> None:
+        if self.graph is None and self.use_graph:
+            self.graph = _capture(self._step, self._written(), self.device, self.sampler is not None)
+
+
+class DecodeSession(_Session):
     """Static buffers + captured graph of the single-token step for one (model, max_seq_length, greedy) choice."""
 
     def __init__(self, model: GPT, max_seq_length: int, max_tokens: int, greedy: bool, use_graph: bool = True,
                  engine: Optional[bool] = None, sampler: Optional[Tuple[float, Optional[int]]] = None) -> None:
-        self.model, self.S, self.greedy = model, max_seq_length, greedy
+        self._open("generate", model, max_seq_length, (max_tokens + 1,), 1, use_graph)
+        self.greedy = greedy
         # (temperature, top_k) of the in-graph sampling step when not greedy; None: the step ends at the logits
         self.sampler = None if greedy else sampler
         self.noise: Optional[torch.Tensor] = None
-        dev = model.transformer.wte.weight.device
-        if dev.type != "cuda":
-            raise ParrotHipError("generate() runs on the HIP device only: move the model to cuda (no CPU fallback)")
-        self.device = dev
-        self.tokens = torch.zeros((max_tokens + 1,), dtype=torch.int64, device=dev)
-        self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.ws = model.workspace(1, dev, 1)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.use_graph = use_graph
-        if model.rope_cache is None:
-            model.rope_cache = model.build_rope_cache(self.tokens)
-        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != 1:
-            model.kv_caches = model.build_kv_caches(self.tokens.view(1, -1), max_seq_length, model.rope_cache[0].size(-1))
+        self.pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.ws = model.workspace(1, self.device, 1)
         self.caches = [(k[0], v[0]) for k, v in model.kv_caches]
         # one launch per token when the model fits the stream engine (csrc/engine.hip), else 5 launches per block
         from ..engine import StreamEngine
@@ -81,13 +172,7 @@ class DecodeSession:
             engine = StreamEngine.faster_than_multi_launch(model, max_seq_length, ENGINE_AUTO_MIN_WINDOW)
         if engine and StreamEngine.supported(model) is None:
             self.eng = StreamEngine(model, self.tokens, self.pos, self.caches, max_seq_length, greedy)
-        # One resident image of the int4 weights: W4K (the multi-launch step's and every prompt's format; the engine keeps
-        # its E4 copy beside it).  The reference-layout buffers are released; state_dict() / get_weight() rebuild them exactly.
-        if RELEASE_REFERENCE_BUFFERS:
-            for m in model.modules():
-                if hasattr(m, "release_reference"):
-                    m.release_reference()
-
+        self._drop_reference_weights()
 
     # one decode step = the launch sequence that gets captured
     def _step(self) -> None:
@@ -119,39 +204,9 @@ class DecodeSession:
         T = prompt.numel()
         self.tokens[:T].copy_(prompt)
         self.pos.zero_()
-        ws = self.model.workspace(T, self.device, 1)
-        ws.pos_is_zero = True  # the prompt starts at position 0: its attention may take the MFMA kernel (no ring wrap in the call)
-        try:
-            logits = self.model.run_rows(ws, self.tokens, None, self.pos, self.S, self.caches, self.model.rope_cache)
-        finally:
-            ws.pos_is_zero = False
+        logits = _run_prompt(self.model, self.tokens, T, self.pos, self.S, self.caches)
         self.pos.fill_(T - 1)
         return logits
-
-    def capture(self) -> None:
-        if self.graph is not None or not self.use_graph:
-            return
-        # warm-up outside capture (lazy W4K repacks, workspace allocations), restoring the loop state afterwards
-        saved = (self.tokens.clone(), self.pos.clone(), [(k.clone(), v.clone()) for k, v in self.caches])
-        # (a sampling step draws from torch's generator: the warm-up below must not use up draws of the caller's seed)
-        rng = torch.cuda.get_rng_state(self.device) if self.sampler is not None else None
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self._step()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
-        with _capturing(graph):
-            self._step()
-        self.graph = graph
-        if rng is not None:
-            torch.cuda.set_rng_state(rng, self.device)
-        self.tokens.copy_(saved[0])
-        self.pos.copy_(saved[1])
-        for (k, v), (k0, v0) in zip(self.caches, saved[2]):
-            k.copy_(k0)
-            v.copy_(v0)
 
     def step(self) -> torch.Tensor:
         """Decode the token at ``pos``; returns the logits buffer (V,) of that step."""
@@ -175,7 +230,7 @@ class DecodeSession:
 # 654 tokens/s behind a 512-token prompt.  "auto" picks by weight format and window size.
 ENGINE_DEFAULT = "auto"
 ENGINE_AUTO_MIN_WINDOW = 1024
-# A decode session frees the reference-layout copy of every GPTQ int4 Linear (quantize/gptq.py::release_reference): Llama-2-7B
+# A decode session frees the reference-layout copy of every GPTQ int4 Linear (quantize/gptq.py): Llama-2-7B
 # int4 then holds 3.5 GB of weights instead of 7 (multi-launch step) and Falcon-40B int4 44 GB instead of 66 (engine: W4K + E4).
 RELEASE_REFERENCE_BUFFERS = True
 MAX_SESSIONS_PER_MODEL = 4  # captured steps kept per model (keyed by window, greedy / sampling parameters), least recently used first out
@@ -226,16 +281,7 @@ def generate(
     reference (generate/base.py:93-159): a 1-D tensor holding the prompt followed by the generated tokens, cut after
     ``eos_id`` when it is produced.  Call ``model.reset_cache()`` between prompts like the reference's ``main``."""
     T = idx.size(0)
-    assert max_returned_tokens > T
-    if not isinstance(model, GPT):
-        raise ParrotHipError("generate() drives lit_parrot_amd.GPT models")
-    assert max_seq_length <= model.config.block_size
-    if max_returned_tokens > model.config.block_size:
-        # positions index the RoPE tables (block_size rows); the reference fails at rope.index_select in this case
-        # (lit_gpt/model.py:88) - here the kernels would read past the tables on the device
-        raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
-                             "positions past the RoPE tables")
-    assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
+    _check_args("generate", model, [T], max_returned_tokens, max_seq_length, length_first=True)
     dtype = idx.dtype
     greedy = top_k == 1 and temperature > 0
     sess = _session(model, max_seq_length, max_returned_tokens, greedy, (float(temperature), top_k))
@@ -261,7 +307,7 @@ def generate(
 
 
 # ------------------------------------------------------------------------------------------------ batched decode
-class BatchDecodeSession:
+class BatchDecodeSession(_Session):
     """Static buffers + captured graph of the batched step: B independent sequences (1 <= B <= 8), one row each.
 
         tokens  int64[B][L]   row b: prompt b, then its sampled tokens
@@ -275,31 +321,25 @@ class BatchDecodeSession:
 
     def __init__(self, model: GPT, B: int, max_seq_length: int, max_tokens: int, greedy: bool,
                  sampler: Optional[Tuple[float, Optional[int]]] = None, eos_id: int = -1, use_graph: bool = True) -> None:
-        self.model, self.B, self.S, self.greedy, self.eos_id = model, B, max_seq_length, greedy, eos_id
+        self._open_rows("generate_batch", model, B, max_seq_length, max_tokens + 1, B, greedy, sampler, eos_id, use_graph,
+                        rows_are_sequences=True)
+        self.caches = list(model.kv_caches)  # (B, n_groups, S, hs) per layer
+        self._drop_reference_weights()
+
+    def _open_rows(self, fn: str, model: GPT, B: int, max_seq_length: int, length: int, kv_batch: int, greedy: bool,
+                   sampler: Optional[Tuple[float, Optional[int]]], eos_id: int, use_graph: bool, **rows) -> None:
+        """The buffers of a step over B rows, each with a token buffer of ``length``; ``rows``: what the rows are to the workspace."""
+        self._open(fn, model, max_seq_length, (B, length), kv_batch, use_graph)
+        self.B, self.greedy, self.eos_id = B, greedy, eos_id
         self.sampler = None if greedy else sampler
-        dev = model.transformer.wte.weight.device
-        if dev.type != "cuda":
-            raise ParrotHipError("generate_batch() runs on the HIP device only: move the model to cuda (no CPU fallback)")
-        self.device = dev
-        self.tokens = torch.zeros((B, max_tokens + 1), dtype=torch.int64, device=dev)
+        dev = self.device
         self.pos = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.end = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.ws = model.workspace(B, dev, B, rows_are_sequences=True)
+        self.ws = model.workspace(B, dev, B, **rows)
         V = model.config.padded_vocab_size
         self.first_logits = torch.empty((B, V), dtype=torch.bfloat16, device=dev)  # the prompts' last rows
         self.noise = torch.empty((B, V), dtype=torch.bfloat16, device=dev) if self.sampler is not None else None
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.use_graph = use_graph
-        if model.rope_cache is None:
-            model.rope_cache = model.build_rope_cache(self.tokens)
-        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != B:
-            model.kv_caches = model.build_kv_caches(self.tokens, max_seq_length, model.rope_cache[0].size(-1))
-        self.caches = list(model.kv_caches)  # (B, n_groups, S, hs) per layer
-        if RELEASE_REFERENCE_BUFFERS:
-            for m in model.modules():
-                if hasattr(m, "release_reference"):
-                    m.release_reference()
 
     def sample(self, logits: torch.Tensor, eos_id: int) -> None:
         """Row b: ``tokens[b, pos[b] + 1]`` = the token drawn from ``logits[b]``, ``pos[b] += 1``, unless the row is frozen.  The noise
@@ -320,40 +360,10 @@ class BatchDecodeSession:
         for b, p in enumerate(prompts):
             T = p.numel()
             self.tokens[b, :T].copy_(p)
-            ws = self.model.workspace(T, self.device, 1)
-            ws.pos_is_zero = True  # the prompt starts at position 0 (see DecodeSession.prefill)
-            try:
-                logits = self.model.run_rows(ws, self.tokens[b], None, self.zero_pos, self.S,
-                                             [(k[b], v[b]) for k, v in self.caches], self.model.rope_cache)
-            finally:
-                ws.pos_is_zero = False
+            logits = _run_prompt(self.model, self.tokens[b], T, self.zero_pos, self.S, [(k[b], v[b]) for k, v in self.caches])
             self.first_logits[b].copy_(logits[0])
         self.pos.copy_(torch.tensor([p.numel() - 1 for p in prompts], dtype=torch.int32))
         self.end.fill_(max_returned_tokens)
-
-    def capture(self) -> None:
-        if self.graph is not None or not self.use_graph:
-            return
-        # warm-up outside capture, restoring the loop state afterwards (as DecodeSession.capture)
-        saved = (self.tokens.clone(), self.pos.clone(), [(k.clone(), v.clone()) for k, v in self.caches])
-        rng = torch.cuda.get_rng_state(self.device) if self.sampler is not None else None
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self._step()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
-        with _capturing(graph):
-            self._step()
-        self.graph = graph
-        if rng is not None:
-            torch.cuda.set_rng_state(rng, self.device)
-        self.tokens.copy_(saved[0])
-        self.pos.copy_(saved[1])
-        for (k, v), (k0, v0) in zip(self.caches, saved[2]):
-            k.copy_(k0)
-            v.copy_(v0)
 
     def step(self) -> None:
         if self.graph is not None:
@@ -366,6 +376,25 @@ class BatchDecodeSession:
         pos = self.pos.long()
         state = torch.stack([pos, self.tokens.gather(1, pos.view(-1, 1)).view(-1), self.end.long()]).cpu()
         return bool(((state[0] + 1 >= state[2]) | (state[1] == self.eos_id)).all())
+
+
+def _decode_rows(sess: BatchDecodeSession, prompts: Sequence[torch.Tensor], max_returned_tokens: int,
+                 eos_id: Optional[int]) -> List[torch.Tensor]:
+    """The loop behind a prefilled session of rows: every row, its prompt included, cut at its position and before ``eos_id``."""
+    sess.capture()
+    sess.sample(sess.first_logits, -1)  # the first token of every row is drawn whatever the prompt's last token is
+    for _ in range(max_returned_tokens - min(p.numel() for p in prompts) - 1):
+        if eos_id is not None and sess.all_frozen():  # host sync, as in generate()
+            break
+        sess.step()
+    tokens, pos = sess.tokens.cpu(), sess.pos.cpu()
+    out = []
+    for b, p in enumerate(prompts):
+        n = int(pos[b]) + 1
+        if eos_id is not None and n > p.numel() and int(tokens[b, n - 1]) == int(eos_id):
+            n -= 1  # the reference returns idx[:input_pos]: the eos token is not part of the result
+        out.append(sess.tokens[b, :n].to(p.dtype).clone())
+    return out
 
 
 def _batch_prompts(prompts: Union[torch.Tensor, Sequence[torch.Tensor]]) -> List[torch.Tensor]:
@@ -400,18 +429,8 @@ def generate_batch(
     of 1-D token tensors (lengths may differ) or a (B, T) tensor.  Every step decodes all rows in one captured batched pass
     (BatchDecodeSession), so the weights are read once per pass instead of once per sequence."""
     prompts = _batch_prompts(prompts)
-    if not isinstance(model, GPT):
-        raise ParrotHipError("generate_batch() drives lit_parrot_amd.GPT models")
-    for p in prompts:  # generate()'s checks, row by row
-        T = p.numel()
-        assert max_returned_tokens > T
-        assert max_seq_length <= model.config.block_size
-        if max_returned_tokens > model.config.block_size:
-            raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
-                                 "positions past the RoPE tables")
-        assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
-    if model.transformer.wte.weight.device.type != "cuda":
-        raise ParrotHipError("generate_batch() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    _check_args("generate_batch", model, [p.numel() for p in prompts], max_returned_tokens, max_seq_length)  # row by row
+    _cuda_device("generate_batch", model)
     why = model.batched_decode_unsupported()
     if why is not None:
         raise ParrotHipError(f"generate_batch: {why}; use generate() per prompt")
@@ -422,20 +441,7 @@ def generate_batch(
     sess = _cached_session(model, ("batch", B, max_seq_length, greedy, sampler, eos), max_returned_tokens,
                            lambda: BatchDecodeSession(model, B, max_seq_length, max_returned_tokens, greedy, sampler, eos))
     sess.prefill([p.to(device=sess.device, dtype=torch.int64) for p in prompts], max_returned_tokens)
-    sess.capture()
-    sess.sample(sess.first_logits, -1)  # the first token of every row is drawn whatever the prompt's last token is
-    for _ in range(max_returned_tokens - min(p.numel() for p in prompts) - 1):
-        if eos_id is not None and sess.all_frozen():  # host sync, as in generate()
-            break
-        sess.step()
-    tokens, pos = sess.tokens.cpu(), sess.pos.cpu()
-    out = []
-    for b, p in enumerate(prompts):
-        n = int(pos[b]) + 1
-        if eos_id is not None and n > p.numel() and int(tokens[b, n - 1]) == eos:
-            n -= 1  # the reference returns idx[:input_pos]: the eos token is not part of the result
-        out.append(sess.tokens[b, :n].to(p.dtype).clone())
-    return out
+    return _decode_rows(sess, prompts, max_returned_tokens, eos_id)
 
 
 # ------------------------------------------------------------------------------------------------ candidates of one prompt
@@ -480,39 +486,19 @@ class CandidateSession(BatchDecodeSession):
 
     def __init__(self, model: GPT, n: int, max_seq_length: int, tail_slots: int, greedy: bool,
                  sampler: Optional[Tuple[float, Optional[int]]] = None, eos_id: int = -1, use_graph: bool = True) -> None:
-        self.model, self.B, self.S, self.greedy, self.eos_id = model, n, max_seq_length, greedy, eos_id
+        # (no position reaches the window's end: the token buffer is as long as the window)
+        self._open_rows("generate_candidates", model, n, max_seq_length, max_seq_length + 1, 1, greedy, sampler, eos_id, use_graph,
+                        rows_share_prefix=True)
         self.S_tail = tail_slots
-        self.sampler = None if greedy else sampler
-        dev = model.transformer.wte.weight.device
-        if dev.type != "cuda":
-            raise ParrotHipError("generate_candidates() runs on the HIP device only: move the model to cuda (no CPU fallback)")
-        self.device = dev
-        c = model.config
-        self.tokens = torch.zeros((n, max_seq_length + 1), dtype=torch.int64, device=dev)  # (no position reaches the window's end)
-        self.pos = torch.zeros((n,), dtype=torch.int32, device=dev)
-        self.end = torch.zeros((n,), dtype=torch.int32, device=dev)
+        dev, c = self.device, model.config
         self.prefix_len = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.ws = model.workspace(n, dev, n, rows_share_prefix=True)
-        V = c.padded_vocab_size
-        self.first_logits = torch.empty((n, V), dtype=torch.bfloat16, device=dev)
-        self.noise = torch.empty((n, V), dtype=torch.bfloat16, device=dev) if self.sampler is not None else None
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.use_graph = use_graph
-        if model.rope_cache is None:
-            model.rope_cache = model.build_rope_cache(self.tokens)
-        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != 1:
-            model.kv_caches = model.build_kv_caches(self.tokens[:1], max_seq_length, model.rope_cache[0].size(-1))
         self.caches = [(k[0], v[0]) for k, v in model.kv_caches]  # the shared prompt cache: (n_groups, S, hs) per layer
         shape = (n, c.n_query_groups, tail_slots, c.head_size)
         self.tails = [(torch.zeros(shape, dtype=torch.bfloat16, device=dev), torch.zeros(shape, dtype=torch.bfloat16, device=dev))
                       for _ in range(c.n_layer)]
         self.prefix_caches = [(ops.PrefixCache(k, tk, self.prefix_len), ops.PrefixCache(v, tv, self.prefix_len))
                               for (k, v), (tk, tv) in zip(self.caches, self.tails)]
-        if RELEASE_REFERENCE_BUFFERS:
-            for m in model.modules():
-                if hasattr(m, "release_reference"):
-                    m.release_reference()
+        self._drop_reference_weights()
 
     def kv_bytes(self) -> int:
         """Bytes of K/V this session holds: the shared cache once and the n tails."""
@@ -522,43 +508,22 @@ class CandidateSession(BatchDecodeSession):
         logits = self.model.run_rows(self.ws, self.tokens, self.pos, self.pos, self.S, self.prefix_caches, self.model.rope_cache)
         self.sample(logits, self.eos_id)
 
+    def _written(self) -> List[torch.Tensor]:
+        # The step writes tokens, pos and tail slots only, never the shared cache.  A tail slot is always written by its own step
+        # before a later step reads it, so the tokens do not need the tails put back; they are, so that capture() leaves no trace
+        # (its warm-up at pos = T - 1 writes slot 0 of every tail)
+        return [self.tokens, self.pos] + [t for kv in self.tails for t in kv]
+
     def prefill(self, prompt: torch.Tensor, max_returned_tokens: int) -> None:
-        """The prompt ONCE through the multi-row path into the shared cache (DecodeSession.prefill); every row starts from its last
-        row's logits at pos = T - 1."""
+        """The prompt ONCE through the multi-row path into the shared cache; every row starts from its last row's logits at
+        pos = T - 1."""
         T = prompt.numel()
         self.tokens[:, :T] = prompt
-        ws = self.model.workspace(T, self.device, 1)
-        ws.pos_is_zero = True  # the prompt starts at position 0 (see DecodeSession.prefill)
-        try:
-            logits = self.model.run_rows(ws, self.tokens[0], None, self.zero_pos, self.S, self.caches, self.model.rope_cache)
-        finally:
-            ws.pos_is_zero = False
+        logits = _run_prompt(self.model, self.tokens[0], T, self.zero_pos, self.S, self.caches)
         self.first_logits.copy_(logits[:1].expand(self.B, -1))
         self.pos.fill_(T - 1)
         self.end.fill_(max_returned_tokens)
         self.prefix_len.fill_(T)
-
-    def capture(self) -> None:
-        if self.graph is not None or not self.use_graph:
-            return
-        # warm-up outside capture, restoring the loop state afterwards (as BatchDecodeSession.capture).  The step writes tokens, pos
-        # and tail slots only; a tail slot is always written by its own step before a later step reads it, so the tails need no restore
-        saved = (self.tokens.clone(), self.pos.clone())
-        rng = torch.cuda.get_rng_state(self.device) if self.sampler is not None else None
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self._step()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
-        with _capturing(graph):
-            self._step()
-        self.graph = graph
-        if rng is not None:
-            torch.cuda.set_rng_state(rng, self.device)
-        self.tokens.copy_(saved[0])
-        self.pos.copy_(saved[1])
 
 
 @torch.no_grad()
@@ -579,15 +544,8 @@ def generate_candidates(
     the one shared prompt cache and each keeps a short cache of its own for the tokens it generates (CandidateSession)."""
     if not isinstance(idx, torch.Tensor) or idx.dim() != 1 or idx.numel() == 0:
         raise ParrotHipError("generate_candidates: the prompt must be a non-empty 1-D token tensor")
-    if not isinstance(model, GPT):
-        raise ParrotHipError("generate_candidates() drives lit_parrot_amd.GPT models")
     T = idx.numel()
-    assert max_returned_tokens > T  # generate()'s checks
-    assert max_seq_length <= model.config.block_size
-    if max_returned_tokens > model.config.block_size:
-        raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
-                             "positions past the RoPE tables")
-    assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
+    _check_args("generate_candidates", model, [T], max_returned_tokens, max_seq_length)
     if not isinstance(n, int) or not 1 <= n <= ops.GEMV_MAX_ROWS:
         raise ParrotHipError(f"generate_candidates: n={n}; the candidates step takes 1 to {ops.GEMV_MAX_ROWS} rows")
     why = model.batched_decode_unsupported()
@@ -597,8 +555,7 @@ def generate_candidates(
         raise ParrotHipError(f"generate_candidates: max_seq_length={max_seq_length} < max_returned_tokens={max_returned_tokens}: the shared "
                              "prompt cache and the candidates' own caches are addressed by position (no sliding window); use "
                              "generate_batch(model, [idx] * n, ...)")
-    if model.transformer.wte.weight.device.type != "cuda":
-        raise ParrotHipError("generate_candidates() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    _cuda_device("generate_candidates", model)
     greedy = top_k == 1 and temperature > 0
     sampler = None if greedy else (float(temperature), top_k)
     eos = -1 if eos_id is None else int(eos_id)
@@ -607,24 +564,25 @@ def generate_candidates(
     key = ("candidates", n, max_seq_length, tail, greedy, sampler, eos, bool(ops.CANDIDATES_SHARE_LOADS))
     sess = _cached_session(model, key, max_returned_tokens, lambda: CandidateSession(model, n, max_seq_length, tail, greedy, sampler, eos))
     sess.prefill(idx.to(device=sess.device, dtype=torch.int64), max_returned_tokens)
-    sess.capture()
-    sess.sample(sess.first_logits, -1)  # the first token of every row is drawn whatever the prompt's last token is
-    for _ in range(max_returned_tokens - T - 1):
-        if eos_id is not None and sess.all_frozen():  # host sync, as in generate()
-            break
-        sess.step()
-    tokens, pos = sess.tokens.cpu(), sess.pos.cpu()
-    out = []
-    for b in range(n):
-        m = int(pos[b]) + 1
-        if eos_id is not None and m > T and int(tokens[b, m - 1]) == eos:
-            m -= 1  # the reference returns idx[:input_pos]: the eos token is not part of the result
-        out.append(sess.tokens[b, :m].to(idx.dtype).clone())
-    return out
+    return _decode_rows(sess, [idx] * n, max_returned_tokens, eos_id)
 
 
 # ------------------------------------------------------------------------------------------------ speculative decode
-class SpeculativeSession:
+def _check_speculative(model: GPT, max_seq_length: int, max_tokens: int, draft_len: int, ngram_max: int, ngram_min: int) -> None:
+    """What the speculative step asks of its parameters, of the model and of the window (session and entry point alike)."""
+    if not 1 <= draft_len <= ops.MAX_DRAFT_LEN:
+        raise ParrotHipError(f"draft_len={draft_len}: the speculative step verifies 1 to {ops.MAX_DRAFT_LEN} drafts")
+    if not 1 <= ngram_min <= ngram_max <= ops.MAX_NGRAM:
+        raise ParrotHipError(f"n-grams {ngram_min} .. {ngram_max}: 1 <= ngram_min <= ngram_max <= {ops.MAX_NGRAM} expected")
+    why = model.speculative_decode_unsupported()
+    if why is not None:
+        raise ParrotHipError(f"generate_speculative: {why}; use generate()")
+    if max_seq_length < max_tokens:
+        raise ParrotHipError(f"generate_speculative: max_seq_length={max_seq_length} < max_returned_tokens={max_tokens}: the "
+                             "rows of a speculative step must not wrap the cache ring (no sliding window); use generate()")
+
+
+class SpeculativeSession(_Session):
     """Greedy decoding of ONE sequence that verifies ``draft_len`` guessed tokens per weight pass (prompt-lookup speculative
     decoding).  The drafts are what followed the last earlier occurrence of the sequence's newest n-gram (``ops.ngram_draft``); the
     token at ``pos`` and the K drafts behind it go through the network as the M = K + 1 rows of one pass, every row bit for bit
@@ -646,39 +604,19 @@ class SpeculativeSession:
 
     def __init__(self, model: GPT, max_seq_length: int, max_tokens: int, draft_len: int = 1, ngram_max: int = 3, ngram_min: int = 1,
                  eos_id: int = -1, use_graph: bool = True, draft_hook: Optional[Callable[["SpeculativeSession"], int]] = None) -> None:
-        if not 1 <= draft_len <= ops.MAX_DRAFT_LEN:
-            raise ParrotHipError(f"draft_len={draft_len}: the speculative step verifies 1 to {ops.MAX_DRAFT_LEN} drafts")
-        if not 1 <= ngram_min <= ngram_max <= ops.MAX_NGRAM:
-            raise ParrotHipError(f"n-grams {ngram_min} .. {ngram_max}: 1 <= ngram_min <= ngram_max <= {ops.MAX_NGRAM} expected")
-        dev = model.transformer.wte.weight.device
-        if dev.type != "cuda":
-            raise ParrotHipError("generate_speculative() runs on the HIP device only: move the model to cuda (no CPU fallback)")
-        why = model.speculative_decode_unsupported()
-        if why is not None:
-            raise ParrotHipError(f"speculative decode: {why}")
-        if max_seq_length < max_tokens:
-            raise ParrotHipError(f"speculative decode: a window of {max_seq_length} slots is shorter than the {max_tokens} tokens: the "
-                                 "rows of a step must not wrap the cache ring")
-        self.model, self.S, self.K, self.M = model, max_seq_length, draft_len, draft_len + 1
+        _check_speculative(model, max_seq_length, max_tokens, draft_len, ngram_max, ngram_min)
+        self._open("generate_speculative", model, max_seq_length, (max_tokens + 1,), 1, use_graph)
+        self.K, self.M = draft_len, draft_len + 1
         self.ngram_max, self.ngram_min, self.eos_id, self.draft_hook = ngram_max, ngram_min, eos_id, draft_hook
-        self.device = dev
-        self.tokens = torch.zeros((max_tokens + 1,), dtype=torch.int64, device=dev)
+        dev = self.device
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.end = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.state = torch.zeros((ops.SPEC_STATE_WORDS,), dtype=torch.int32, device=dev)
         self.ws_one = model.workspace(1, dev, 1)
         self.ws_rows = model.workspace(self.M, dev, self.M, rows_are_drafts=True)
         self.graphs: Dict[bool, torch.cuda.CUDAGraph] = {}  # True: the M-row step, False: the one-row step
-        self.use_graph = use_graph
-        if model.rope_cache is None:
-            model.rope_cache = model.build_rope_cache(self.tokens)
-        if not model.kv_caches or model.kv_caches[0][0].size(2) != max_seq_length or model.kv_caches[0][0].size(0) != 1:
-            model.kv_caches = model.build_kv_caches(self.tokens.view(1, -1), max_seq_length, model.rope_cache[0].size(-1))
         self.caches = [(k[0], v[0]) for k, v in model.kv_caches]
-        if RELEASE_REFERENCE_BUFFERS:
-            for m in model.modules():
-                if hasattr(m, "release_reference"):
-                    m.release_reference()
+        self._drop_reference_weights()
 
     def draft(self) -> None:
         """The lookup kernel (the hook, when there is one, is called by the loop instead: it is host code)."""
@@ -704,46 +642,21 @@ class SpeculativeSession:
         self.pos.zero_()
         self.end.fill_(max_returned_tokens)
         self.state.zero_()
-        ws = self.model.workspace(T, self.device, 1)
-        ws.pos_is_zero = True
-        try:
-            logits = self.model.run_rows(ws, self.tokens, None, self.pos, self.S, self.caches, self.model.rope_cache)
-        finally:
-            ws.pos_is_zero = False
+        logits = _run_prompt(self.model, self.tokens, T, self.pos, self.S, self.caches)
         self.pos.fill_(T - 1)
         return logits
+
+    def _written(self) -> List[torch.Tensor]:
+        return super()._written() + [self.state]
 
     def capture(self, rows: bool = True) -> None:
         """Capture the one-row step and, with ``rows``, the M-row step (each once).  The warm-up runs at the position the prompt
         left: the caller passes ``rows`` only when ``pos + M`` is inside every buffer there."""
         if not self.use_graph:
             return
-        # warm-up outside capture and restore of the loop state afterwards, as DecodeSession.capture
-        saved = (self.tokens.clone(), self.pos.clone(), self.state.clone(), [(k.clone(), v.clone()) for k, v in self.caches])
-
-        def restore() -> None:
-            self.tokens.copy_(saved[0])
-            self.pos.copy_(saved[1])
-            self.state.copy_(saved[2])
-            for (k, v), (k0, v0) in zip(self.caches, saved[3]):
-                k.copy_(k0)
-                v.copy_(v0)
-
         for is_rows, step in ((True, self._step_rows), (False, self._step_one)):
-            if is_rows in self.graphs or (is_rows and not rows):
-                continue
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                step()
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            torch.cuda.synchronize(self.device)
-            restore()
-            graph = torch.cuda.CUDAGraph()
-            with _capturing(graph):
-                step()
-            self.graphs[is_rows] = graph
-            restore()
+            if is_rows not in self.graphs and (rows or not is_rows):
+                self.graphs[is_rows] = _capture(step, self._written(), self.device, False)
 
     def step(self, rows: bool) -> torch.Tensor:
         """One step: the M-row verification pass (``rows``) or the one-row step; returns that pass's logits buffer."""
@@ -781,26 +694,9 @@ def generate_speculative(
     ``(tokens, {"steps": weight passes after the prompt, "accepted": drafts kept, "matched_steps": passes that verified drafts})``.
     ``draft_hook`` (tests, tools/spec_bench.py) replaces the lookup, see SpeculativeSession."""
     T = idx.size(0)
-    assert max_returned_tokens > T
-    if not isinstance(model, GPT):
-        raise ParrotHipError("generate_speculative() drives lit_parrot_amd.GPT models")
-    assert max_seq_length <= model.config.block_size
-    if max_returned_tokens > model.config.block_size:
-        raise ParrotHipError(f"max_returned_tokens={max_returned_tokens} exceeds block_size={model.config.block_size}: "
-                             "positions past the RoPE tables")
-    assert max_seq_length >= T, f"Cannot forward sequence of length {T}, max seq length is only {max_seq_length}"
-    if not 1 <= draft_len <= ops.MAX_DRAFT_LEN:
-        raise ParrotHipError(f"draft_len={draft_len}: the speculative step verifies 1 to {ops.MAX_DRAFT_LEN} drafts")
-    if not 1 <= ngram_min <= ngram_max <= ops.MAX_NGRAM:
-        raise ParrotHipError(f"n-grams {ngram_min} .. {ngram_max}: 1 <= ngram_min <= ngram_max <= {ops.MAX_NGRAM} expected")
-    why = model.speculative_decode_unsupported()
-    if why is not None:
-        raise ParrotHipError(f"generate_speculative: {why}; use generate()")
-    if max_seq_length < max_returned_tokens:
-        raise ParrotHipError(f"generate_speculative: max_seq_length={max_seq_length} < max_returned_tokens={max_returned_tokens}: the "
-                             "rows of a speculative step must not wrap the cache ring (no sliding window); use generate()")
-    if model.transformer.wte.weight.device.type != "cuda":
-        raise ParrotHipError("generate_speculative() runs on the HIP device only: move the model to cuda (no CPU fallback)")
+    _check_args("generate_speculative", model, [T], max_returned_tokens, max_seq_length, length_first=True)
+    _check_speculative(model, max_seq_length, max_returned_tokens, draft_len, ngram_max, ngram_min)
+    _cuda_device("generate_speculative", model)
     eos = -1 if eos_id is None else int(eos_id)
     make = lambda: SpeculativeSession(model, max_seq_length, max_returned_tokens, draft_len, ngram_max, ngram_min, eos,  # noqa: E731
                                       draft_hook=draft_hook)

@@ -227,31 +227,23 @@ class GPT(nn.Module):
     def batched_decode_unsupported(self) -> Optional[str]:
         """Why the batched decode step (one row per sequence, ``Workspace(rows_are_sequences=True)``) cannot run this model,
         or None when it can."""
-        from .quantize.bnb import InferenceLinear8bitLt
-
-        c = self.config
-        if hasattr(self, "adapter_kv_caches") or any(hasattr(m, "adapter_scale") or hasattr(m, "adapter_bias") for m in self.modules()):
-            return "adapter models decode one sequence at a time (the prefix / adapter-v2 terms are built for one row)"
-        if any(isinstance(m, InferenceLinear8bitLt) for m in self.modules()):
-            return ("LLM.int8 Linears decode one sequence at a time: the multi-row activation quantiser takes the outlier columns "
-                    "of all rows together, so one sequence's output would depend on the others")
-        if c.q_per_kv > ops.FUSED_ATTN_MAX_Q_PER_KV:
-            return f"{c.q_per_kv} query heads per K/V group: the batched attention is built for at most {ops.FUSED_ATTN_MAX_Q_PER_KV}"
-        if c.head_size not in (32, 64, 128):
-            return f"head size {c.head_size}: the batched attention is built for 32, 64 and 128"
-        return None
+        return self._rows_decode_unsupported()
 
     def speculative_decode_unsupported(self) -> Optional[str]:
         """Why the speculative decode step (``Workspace(rows_are_drafts=True)``: a token and its drafts as the rows of one pass, each
         row bit for bit the one-row step) cannot run this model, or None when it can."""
+        return self._rows_decode_unsupported()
+
+    def _rows_decode_unsupported(self) -> Optional[str]:
+        """Why a decode step of several rows (sequences, candidates or drafts) cannot run this model, or None when it can."""
         from .quantize.bnb import InferenceLinear8bitLt
 
         c = self.config
-        if any(isinstance(m, InferenceLinear8bitLt) for m in self.modules()):
-            return ("LLM.int8 Linears: the multi-row activation quantiser takes the outlier columns of all rows together, so a "
-                    "verified row would not equal the one-row step")
         if hasattr(self, "adapter_kv_caches") or any(hasattr(m, "adapter_scale") or hasattr(m, "adapter_bias") for m in self.modules()):
-            return "adapter models: the prefix / adapter-v2 terms are built for the one-row step"
+            return "adapter models decode one row at a time (the prefix / adapter-v2 terms are built for the one-row step)"
+        if any(isinstance(m, InferenceLinear8bitLt) for m in self.modules()):
+            return ("LLM.int8 Linears decode one row at a time: the multi-row activation quantiser takes the outlier columns "
+                    "of all rows together, so a row's output would depend on the other rows and not equal the one-row step")
         if c.q_per_kv > ops.FUSED_ATTN_MAX_Q_PER_KV:
             return f"{c.q_per_kv} query heads per K/V group: the fused decode attention is built for at most {ops.FUSED_ATTN_MAX_Q_PER_KV}"
         if c.head_size not in (32, 64, 128):

@@ -267,3 +267,60 @@ def test_the_prompt_is_prefilled_and_stored_once(engine_off, split_keys_32, shar
     assert _count(prof, lambda k: k == "attn_fused_decode_prefix") == 2 * cfg.n_layer * steps
     assert _count(prof, lambda k: k == "attn_fused_decode_rows") == 0
     assert _count(prof, lambda k: k == "embedding_rows") == steps and _count(prof, lambda k: k == "argmax_advance_rows") == steps + 1
+
+
+# ---- 5. capture() leaves every session as the prompt left it
+def _single(model, greedy):
+    return gb.DecodeSession(model, 32, 32, greedy, sampler=None if greedy else (0.8, 20))
+
+
+SESSIONS = {
+    "single-greedy": (lambda m: _single(m, True), lambda s, p: s.prefill(p[0])),
+    "single-sampled": (lambda m: _single(m, False), lambda s, p: s.prefill(p[0])),
+    "batch": (lambda m: gb.BatchDecodeSession(m, 2, 32, 32, False, (0.8, 20)), lambda s, p: s.prefill(p, 32)),
+    "candidates": (lambda m: gb.CandidateSession(m, 2, 32, gb.candidate_tail_slots(32, 8), False, (0.8, 20)), lambda s, p: s.prefill(p[0], 32)),
+    "speculative": (lambda m: gb.SpeculativeSession(m, 32, 32, draft_len=2), lambda s, p: s.prefill(p[0], 32)),
+}
+
+
+@pytest.mark.parametrize("kind", list(SESSIONS))
+def test_capture_restores_what_the_step_writes(kind):
+    """After an 8-token prompt in a window of 32: capture() (a warm-up step and the capture itself) leaves tokens, pos, end, state,
+    every K/V cache and tail and the device generator bit for bit as they were, a second capture() keeps the graph(s), and a step
+    then advances."""
+    cfg = Config.from_name("tiny-llama")
+    model = L.GPT(cfg)
+    model.load_state_dict({k: v.to(BF) for k, v in synthetic_state_dict(cfg, MODEL_SEED, perturb=True).items()}, strict=True)
+    model = model.to(BF).to(DEV).eval()
+    make, prefill = SESSIONS[kind]
+    sess = make(model)
+    speculative = kind == "speculative"
+    torch.manual_seed(SEED)
+    with torch.no_grad():
+        prefill(sess, [prompt_of(cfg, 8), synthetic_prompt(cfg, 8, 3).to(DEV)])
+
+        def snapshot():
+            named = {n: getattr(sess, n) for n in ("tokens", "pos", "end", "state") if hasattr(sess, n)}
+            for i, (k, v) in enumerate(sess.caches + getattr(sess, "tails", [])):
+                named[f"k{i}"], named[f"v{i}"] = k, v
+            named["generator"] = torch.cuda.get_rng_state(DEV)
+            return {n: t.clone() for n, t in named.items()}
+
+        def graphs():
+            return list(sess.graphs.values()) if speculative else [sess.graph]
+
+        before = snapshot()
+        assert int(before["pos"].min()) == 7 and bool(before["k0"].any()), "the prompt is not in the session"
+        sess.capture()
+        after = snapshot()
+        assert before.keys() == after.keys()
+        for n in before:
+            assert torch.equal(before[n], after[n]), f"{kind}: capture() changed {n}"
+        captured = graphs()
+        assert len(captured) == (2 if speculative else 1) and all(g is not None for g in captured)
+        sess.capture()
+        assert all(a is b for a, b in zip(captured, graphs())) and len(graphs()) == len(captured), f"{kind}: captured twice"
+        sess.step(True) if speculative else sess.step()
+        assert bool((sess.pos > before["pos"]).all()), f"{kind}: pos did not advance"
+        if speculative:
+            assert int(sess.state[ops.SPEC_POS]) == int(sess.pos) > int(before["state"][ops.SPEC_POS])
