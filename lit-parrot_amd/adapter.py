@@ -79,10 +79,10 @@ class GPT(BaseModel):
         self.adapter_kv_caches = [block.attn.prefix_kv() for block in self.transformer.h]
 
     def run_rows(self, ws: Workspace, tokens: torch.Tensor, tok_pos: Optional[torch.Tensor], pos: torch.Tensor, S: int,
-                 caches: List[KVCache], rope: RoPECache, *, rope_local: bool = False) -> torch.Tensor:
+                 caches: List[KVCache], rope: RoPECache, *, rope_local: bool = False, pos_is_zero: bool = False) -> torch.Tensor:
         if not self.adapter_kv_caches:  # first call after construction / reset_cache(): outside any capture (prefill, warm-up)
             self.fill_adapter_prefix(ws.x.device)
-        return super().run_rows(ws, tokens, tok_pos, pos, S, caches, rope, rope_local=rope_local)
+        return super().run_rows(ws, tokens, tok_pos, pos, S, caches, rope, rope_local=rope_local, pos_is_zero=pos_is_zero)
 
     def forward(self, idx: torch.Tensor, max_seq_length: Optional[int] = None, input_pos: Optional[torch.Tensor] = None,
                 lm_head_chunk_size: int = 0) -> Union[torch.Tensor, List[torch.Tensor]]:

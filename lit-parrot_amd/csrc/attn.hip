@@ -15,6 +15,8 @@
 // registers and the states are merged once at the end through LDS.
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "parrot_common.h"
 
 namespace parrot {
@@ -134,37 +136,6 @@ rope_kvappend8_kernel(const bf16_t* __restrict__ qkv, int ldqkv, int M, const __
 
 // ------------------------------------------------------------------------------------------ decode attention
 constexpr int kAttnWaves = 4;
-
-// sum over the LPR lanes that share a key row (LPR = 4, 8 or 16 consecutive lanes); every lane of the group gets the
-// total.  DPP only: no LDS crossbar (ds_bpermute) and no lgkmcnt waits in the key loop's dependent chain.
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-    v += dpp0<0xB1>(v);                    // quad_perm [1,0,3,2]
-    v += dpp0<0x4E>(v);                    // quad_perm [2,3,0,1]
-    if (LPR >= 8) v += dpp0<0x141>(v);     // row_half_mirror: the two quads of an 8-lane group
-    if (LPR >= 16) v += dpp0<0x128>(v);    // row_ror:8: the two halves of a 16-lane row
-    return v;
-}
-
-// all-reduce over the 64 / LPR row slots of a wave (lanes with the same lane % LPR): DPP rotations inside the 16-lane rows,
-// then the gfx950 lane swaps across rows (v_permlane16_swap / v_permlane32_swap with both operands the same register
-// return the two halves, which are then combined) - no ds_bpermute.
-template <int LPR, bool MAX>
-__device__ __forceinline__ float slot_allreduce(float v) {
-    auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : a + b; };
-    if (LPR <= 4) v = op(v, dpp0<0x124>(v));  // row_ror:4
-    if (LPR <= 8) v = op(v, dpp0<0x128>(v));  // row_ror:8 - every lane now holds its 16-lane row's result
-    {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));  // rows 0+1 and 2+3
-    }
-    {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));  // both halves
-    }
-    return v;
-}
-
 
 // partial state layout in the workspace: [M][n_head][nsplit][hs + 2] floats: acc[hs], m, l
 // HQ = query heads of the group processed in one pass over the K/V rows (1 for MHA, up to 4 for GQA/MQA)
@@ -812,58 +783,92 @@ attn_fused_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restric
     }
 }
 
-// B > 0 (ROWS): B sequences of one row each, strides in `rows`; SEQ: B consecutive rows of one sequence
-template <int HS, bool AD = false, bool ROWS = false, bool SEQ = false>
-static int attn_fused_launch(const void* qkv, const void* cosp, const void* sinp, int n_elem, const int32_t* pos,
-                             void* k_cache, void* v_cache, int n_groups, int q_per_kv, int S, int nsplit, void* ws,
-                             void* tickets, void* y, int softmax_mode, hipStream_t st, AdapterAttnArgs aa = {},
-                             int B = 1, AttnRowsArgs rows = {}) {
-    const int hq = q_per_kv == 1 ? 1 : (q_per_kv == 2 ? 2 : 4);
-    // 16 waves when a split holds more keys than 4 waves cover in two steps
-    const int per = (S + nsplit - 1) / nsplit;
-    const bool wide = per > 2 * kAttnWaves * (64 / (HS / 8));
-    const dim3 grid(n_groups, nsplit, B * ((q_per_kv + hq - 1) / hq)), block((wide ? 16 : kAttnWaves) * 64);
-    const int kid = SEQ ? K_ATTN_FUSED_SEQ : (ROWS ? K_ATTN_FUSED_ROWS : K_ATTN_FUSED);
-#define PARROT_FUSED_GO(HQV, WV)                                                                                            \
-    do {                                                                                                                    \
-        if (softmax_mode == 1)                                                                                              \
-            return launch(kid, attn_fused_decode_kernel<HS, HQV, 16, true, AD, ROWS, SEQ>, grid, dim3(16 * 64), 0, st, (const bf16_t*)qkv, \
-                          (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups, \
-                          q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa, rows);   \
-        return launch(kid, attn_fused_decode_kernel<HS, HQV, WV, false, AD, ROWS, SEQ>, grid, block, 0, st, (const bf16_t*)qkv, \
-                      (const __half*)cosp, (const __half*)sinp, n_elem, pos, (bf16_t*)k_cache, (bf16_t*)v_cache, n_groups,   \
-                      q_per_kv, S, nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, g_attn_dbg_host, aa, rows);       \
-    } while (0)
-    if (wide) {
-        if (q_per_kv == 1) PARROT_FUSED_GO(1, 16);
-        if (q_per_kv == 2) PARROT_FUSED_GO(2, 16);
-        PARROT_FUSED_GO(4, 16);
+// ------------------------------------------------------------------------------------------ host: one fused decode call
+// What a fused decode call consists of.  Every extern "C" entry point fills one, field by name, and names its kind;
+// check_fused_call and the launch functions read nothing else.  What a kind does not have stays 0.
+enum class FusedKind { OneRow, Rows, Seq, Prefix };  // Rows: B sequences of one row each; Seq: B consecutive rows of one sequence
+
+struct FusedAttnCall {
+    const void* qkv;
+    int ldqkv, B;  // (one row: 0, 1)
+    const void *rope_cos, *rope_sin;
+    int n_elem;
+    const int32_t* pos;
+    int n_groups, q_per_kv, hs, S, nsplit;
+    void *workspace, *tickets;
+    int n_tickets;
+    void *k_cache, *v_cache;
+    int64_t kv_bstride;  // Rows only, else 0
+    void* y;
+    int ldy, softmax_mode;
+    hipStream_t st;
+    // Prefix only: the rows' own tails behind the shared cache
+    const int32_t* prefix_len;
+    void *k_tail, *v_tail;
+    int S_tail, share_loads;
+};
+
+// The run-time to compile-time choices of the launches below, each written once: f receives std::integral_constant values.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+template <typename F>
+static int with_head_size(const char* who, int hs, F&& f) {
+    switch (hs) {
+        case 32: return f(int_c<32>{});
+        case 64: return f(int_c<64>{});
+        case 128: return f(int_c<128>{});
+        default: break;
     }
-    if (q_per_kv == 1) PARROT_FUSED_GO(1, kAttnWaves);
-    if (q_per_kv == 2) PARROT_FUSED_GO(2, kAttnWaves);
-    PARROT_FUSED_GO(4, kAttnWaves);
-#undef PARROT_FUSED_GO
+    set_error("%s: head size %d not built (32, 64, 128)", who, hs);
+    return PARROT_EUNSUPPORTED;
+}
+
+// query heads of a group per pass over its K/V rows
+template <typename F>
+static int with_heads_per_pass(int q_per_kv, F&& f) {
+    if (q_per_kv == 1) return f(int_c<1>{});
+    if (q_per_kv == 2) return f(int_c<2>{});
+    return f(int_c<4>{});
+}
+
+// f(waves, PM) of the fused kernels: "softmax_mode 1" always runs 16 waves; the default softmax runs 16 waves when a split holds
+// more keys than kAttnWaves waves cover in two steps, else kAttnWaves
+template <int HS, typename F>
+static int with_waves(int S, int nsplit, int softmax_mode, F&& f) {
+    const int per = (S + nsplit - 1) / nsplit;
+    if (softmax_mode == 1) return f(int_c<16>{}, std::true_type{});
+    if (per > 2 * kAttnWaves * (64 / (HS / 8))) return f(int_c<16>{}, std::false_type{});
+    return f(int_c<kAttnWaves>{}, std::false_type{});
+}
+
+template <int HS, bool AD = false, bool ROWS = false, bool SEQ = false>
+static int attn_fused_launch(const FusedAttnCall& c, AdapterAttnArgs aa = {}) {
+    const int kid = SEQ ? K_ATTN_FUSED_SEQ : (ROWS ? K_ATTN_FUSED_ROWS : K_ATTN_FUSED);
+    const AttnRowsArgs rows{c.ldqkv, c.ldy, c.kv_bstride};
+    return with_heads_per_pass(c.q_per_kv, [&](auto hq) {
+        return with_waves<HS>(c.S, c.nsplit, c.softmax_mode, [&](auto w, auto pm) {
+            constexpr int HQ = decltype(hq)::value, W = decltype(w)::value;
+            const dim3 grid(c.n_groups, c.nsplit, c.B * ((c.q_per_kv + HQ - 1) / HQ));
+            return launch(kid, attn_fused_decode_kernel<HS, HQ, W, decltype(pm)::value, AD, ROWS, SEQ>, grid, dim3(W * 64), 0, c.st,
+                          (const bf16_t*)c.qkv, (const __half*)c.rope_cos, (const __half*)c.rope_sin, c.n_elem, c.pos, (bf16_t*)c.k_cache,
+                          (bf16_t*)c.v_cache, c.n_groups, c.q_per_kv, c.S, c.nsplit, (float*)c.workspace, (unsigned int*)c.tickets,
+                          (bf16_t*)c.y, g_attn_dbg_host, aa, rows);
+        });
+    });
 }
 
 template <int HS>
 static int attn_launch(const void* q, int M, const int32_t* pos, const void* k_cache, const void* v_cache, int n_groups,
                        int q_per_kv, int S, int nsplit, void* ws, void* y, int ldy, int softmax_mode, hipStream_t st) {
     const dim3 grid(n_groups, nsplit, M), block(kAttnWaves * 64);
-    int rc;
-#define PARROT_ATTN_GO(HQV)                                                                                          \
-    rc = softmax_mode == 1                                                                                            \
-        ? launch(K_ATTN_DECODE, attn_decode_kernel<HS, HQV, true>, grid, block, 0, st, (const bf16_t*)q, pos,         \
-                 (const bf16_t*)k_cache, (const bf16_t*)v_cache, n_groups, q_per_kv, S, nsplit, (float*)ws, (bf16_t*)y, ldy) \
-        : launch(K_ATTN_DECODE, attn_decode_kernel<HS, HQV>, grid, block, 0, st, (const bf16_t*)q, pos,                \
-                (const bf16_t*)k_cache, (const bf16_t*)v_cache, n_groups, q_per_kv, S, nsplit, (float*)ws, (bf16_t*)y, ldy)
-    if (q_per_kv == 1) {
-        PARROT_ATTN_GO(1);
-    } else if (q_per_kv == 2) {
-        PARROT_ATTN_GO(2);
-    } else {
-        PARROT_ATTN_GO(4);
-    }
-#undef PARROT_ATTN_GO
+    const int rc = with_heads_per_pass(q_per_kv, [&](auto hq) {
+        auto go = [&](auto pm) {
+            return launch(K_ATTN_DECODE, attn_decode_kernel<HS, decltype(hq)::value, decltype(pm)::value>, grid, block, 0, st, (const bf16_t*)q,
+                          pos, (const bf16_t*)k_cache, (const bf16_t*)v_cache, n_groups, q_per_kv, S, nsplit, (float*)ws, (bf16_t*)y, ldy);
+        };
+        return softmax_mode == 1 ? go(std::true_type{}) : go(std::false_type{});
+    });
     if (rc != PARROT_OK || nsplit == 1) return rc;
     return launch(K_ATTN_COMBINE, attn_combine_kernel<HS>, dim3(n_groups * q_per_kv, M), dim3(HS), 0, st, (const float*)ws,
                   nsplit, (bf16_t*)y, ldy, n_groups * q_per_kv);
@@ -1198,38 +1203,105 @@ attn_prefix_decode_kernel(const bf16_t* __restrict__ qkv, const __half* __restri
 
 // both launches of one layer (see above); the per-row launch always runs
 template <int HS>
-static int attn_prefix_launch(const void* qkv, const void* cosp, const void* sinp, int n_elem, const int32_t* pos, const void* k_cache,
-                              const void* v_cache, int n_groups, int q_per_kv, int S, int nsplit, void* ws, void* tickets, void* y,
-                              int softmax_mode, hipStream_t st, int B, AttnPrefixArgs pa) {
-    const int hq = q_per_kv == 1 ? 1 : (q_per_kv == 2 ? 2 : 4);
-    const int per = (S + nsplit - 1) / nsplit;
-    const bool wide = per > 2 * kAttnWaves * (64 / (HS / 8));  // the rows kernel's decision
-#define PARROT_PREFIX_GO(HQV, WV, PMV, KINDV, GRID)                                                                                      \
-    launch(K_ATTN_FUSED_PREFIX, attn_prefix_decode_kernel<HS, HQV, WV, PMV, KINDV>, GRID, dim3(WV * 64), 0, st, (const bf16_t*)qkv,        \
-           (const __half*)cosp, (const __half*)sinp, n_elem, pos, (const bf16_t*)k_cache, (const bf16_t*)v_cache, n_groups, q_per_kv, S,  \
-           nsplit, (float*)ws, (unsigned int*)tickets, (bf16_t*)y, pa)
-    pa.share = pa.share != 0 && nsplit > 1 && q_per_kv <= 2 && B > 1;
-    if (pa.share) {
-        const int R = 4 / q_per_kv;
-        const dim3 grid2(n_groups, nsplit - 1, (B + R - 1) / R);  // (the last split is never shared)
-        const int rc = wide ? PARROT_PREFIX_GO(4, 16, false, 2, grid2) : PARROT_PREFIX_GO(4, kAttnWaves, false, 2, grid2);
+static int attn_prefix_launch(const FusedAttnCall& c) {
+    AttnPrefixArgs pa{c.ldqkv, c.ldy, (bf16_t*)c.k_tail, (bf16_t*)c.v_tail, c.prefix_len, c.S_tail, c.B, c.share_loads};
+    pa.share = pa.share != 0 && c.nsplit > 1 && c.q_per_kv <= 2 && c.B > 1;
+    auto go = [&](auto hq, auto w, auto pm, auto kind, dim3 grid) {
+        constexpr int W = decltype(w)::value;
+        return launch(K_ATTN_FUSED_PREFIX, attn_prefix_decode_kernel<HS, decltype(hq)::value, W, decltype(pm)::value, decltype(kind)::value>,
+                      grid, dim3(W * 64), 0, c.st, (const bf16_t*)c.qkv, (const __half*)c.rope_cos, (const __half*)c.rope_sin, c.n_elem, c.pos,
+                      (const bf16_t*)c.k_cache, (const bf16_t*)c.v_cache, c.n_groups, c.q_per_kv, c.S, c.nsplit, (float*)c.workspace,
+                      (unsigned int*)c.tickets, (bf16_t*)c.y, pa);
+    };
+    if (pa.share) {  // KIND 2 is built for HQ = 4 and the default softmax only; its waves are the rows kernel's decision
+        const int R = 4 / c.q_per_kv;
+        const dim3 grid2(c.n_groups, c.nsplit - 1, (c.B + R - 1) / R);  // (the last split is never shared)
+        const int rc = with_waves<HS>(c.S, c.nsplit, 0, [&](auto w, auto) { return go(int_c<4>{}, w, std::false_type{}, int_c<2>{}, grid2); });
         if (rc != PARROT_OK) return rc;
     }
-    const dim3 grid(n_groups, nsplit, B * ((q_per_kv + hq - 1) / hq));
-    if (softmax_mode == 1) {
-        if (q_per_kv == 1) return PARROT_PREFIX_GO(1, 16, true, 1, grid);
-        if (q_per_kv == 2) return PARROT_PREFIX_GO(2, 16, true, 1, grid);
-        return PARROT_PREFIX_GO(4, 16, true, 1, grid);
+    return with_heads_per_pass(c.q_per_kv, [&](auto hq) {
+        const dim3 grid(c.n_groups, c.nsplit, c.B * ((c.q_per_kv + decltype(hq)::value - 1) / decltype(hq)::value));
+        return with_waves<HS>(c.S, c.nsplit, c.softmax_mode, [&](auto w, auto pm) { return go(hq, w, pm, int_c<1>{}, grid); });
+    });
+}
+
+// softmax_mode 1 needs the whole window in one key block of the reference's kernel: one split, at most 512 slots
+static int check_softmax_mode(const char* who, int softmax_mode, int S, int nsplit) {
+    PARROT_REQUIRE(softmax_mode == 0 || softmax_mode == 1, "%s: softmax_mode must be 0 or 1", who);
+    PARROT_UNSUPPORTED(softmax_mode == 0 || (nsplit == 1 && S <= 512),
+                       "%s: softmax_mode 1 (the reference's bf16 probabilities) is built for one split and windows up to 512 slots (S=%d nsplit=%d)", who, S, nsplit);
+    return PARROT_OK;
+}
+
+// every condition of a fused decode call, once and in one order; `who` names the entry point in the messages (the head size is
+// refused by with_head_size)
+static int check_fused_call(const char* who, const FusedAttnCall& c, FusedKind kind) {
+    const bool rows = kind != FusedKind::OneRow, prefix = kind == FusedKind::Prefix;
+    PARROT_REQUIRE(!rows || (c.B >= 1 && c.B <= kMaxDecodeRows), "%s: B=%d (1 .. %d)", who, c.B, kMaxDecodeRows);
+    {
+        const int rc = check_softmax_mode(who, c.softmax_mode, c.S, c.nsplit);
+        if (rc != PARROT_OK) return rc;
     }
-    if (wide) {
-        if (q_per_kv == 1) return PARROT_PREFIX_GO(1, 16, false, 1, grid);
-        if (q_per_kv == 2) return PARROT_PREFIX_GO(2, 16, false, 1, grid);
-        return PARROT_PREFIX_GO(4, 16, false, 1, grid);
+    PARROT_REQUIRE(c.qkv && c.pos && c.k_cache && c.v_cache && c.y && (!prefix || (c.prefix_len && c.k_tail && c.v_tail)), "%s: null pointer", who);
+    const bool shape_ok = c.n_groups >= 1 && c.q_per_kv >= 1 && c.S >= 1;
+    if (prefix) PARROT_REQUIRE(shape_ok && c.S_tail >= 1, "%s: bad shape (S=%d S_tail=%d)", who, c.S, c.S_tail);
+    PARROT_REQUIRE(shape_ok, "%s: bad shape", who);
+    PARROT_UNSUPPORTED(c.q_per_kv <= kFusedMaxQ, "%s: at most %d query heads per group (got %d)", who, kFusedMaxQ, c.q_per_kv);
+    PARROT_REQUIRE(c.n_elem % 2 == 0 && c.n_elem >= 0 && c.n_elem <= c.hs, "%s: bad n_elem=%d", who, c.n_elem);
+    PARROT_REQUIRE(c.n_elem == 0 || (c.rope_cos && c.rope_sin), "%s: rope tables missing", who);
+    PARROT_REQUIRE(c.nsplit >= 1 && c.nsplit <= 65535, "%s: nsplit out of range", who);
+    PARROT_REQUIRE(c.nsplit == 1 || (c.workspace && c.tickets), "%s: workspace and tickets required when nsplit > 1", who);
+    if (rows) {
+        const int n_head = c.n_groups * c.q_per_kv;
+        PARROT_REQUIRE(!c.tickets || c.n_tickets >= c.B * n_head, "%s: %d tickets, B * n_head = %d needed", who, c.n_tickets, c.B * n_head);
+        PARROT_REQUIRE(c.ldqkv >= c.n_groups * (c.q_per_kv + 2) * c.hs && c.ldqkv % 8 == 0, "%s: ldqkv=%d too small or not a multiple of 8", who, c.ldqkv);
+        PARROT_REQUIRE(c.ldy >= n_head * c.hs, "%s: ldy=%d too small", who, c.ldy);
     }
-    if (q_per_kv == 1) return PARROT_PREFIX_GO(1, kAttnWaves, false, 1, grid);
-    if (q_per_kv == 2) return PARROT_PREFIX_GO(2, kAttnWaves, false, 1, grid);
-    return PARROT_PREFIX_GO(4, kAttnWaves, false, 1, grid);
-#undef PARROT_PREFIX_GO
+    PARROT_REQUIRE(kind != FusedKind::Rows || (c.kv_bstride >= (int64_t)c.n_groups * c.S * c.hs && c.kv_bstride % 8 == 0),
+                   "%s: kv_bstride=%lld below n_groups * S * hs or not a multiple of 8", who, (long long)c.kv_bstride);
+    PARROT_REQUIRE(kind != FusedKind::Seq || c.B <= c.S, "%s: M=%d rows do not fit a cache of %d slots", who, c.B, c.S);
+    PARROT_REQUIRE(aligned16(c.qkv) && aligned16(c.k_cache) && aligned16(c.v_cache) && (!prefix || (aligned16(c.k_tail) && aligned16(c.v_tail))),
+                   "%s: 16-byte alignment", who);
+    return PARROT_OK;
+}
+
+// check, then the launch of the kind; `aa`: the one-row call of an adapter layer
+static int fused_attn_call(const char* who, const FusedAttnCall& c, FusedKind kind, const AdapterAttnArgs* aa = nullptr) {
+    const int rc = check_fused_call(who, c, kind);
+    if (rc != PARROT_OK) return rc;
+    return with_head_size(who, c.hs, [&](auto hs) {
+        constexpr int HS = decltype(hs)::value;
+        switch (kind) {
+            case FusedKind::OneRow: return aa ? attn_fused_launch<HS, true>(c, *aa) : attn_fused_launch<HS>(c);
+            case FusedKind::Rows: return attn_fused_launch<HS, false, true>(c);
+            case FusedKind::Seq: return attn_fused_launch<HS, false, true, true>(c);
+            default: return attn_prefix_launch<HS>(c);
+        }
+    });
+}
+
+// the one-row call of both one-row entry points (`aa`: an adapter layer's): one row, no row strides, n_head tickets
+static int one_row_call(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos, int n_groups,
+                        int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets, void* k_cache, void* v_cache, void* y,
+                        int softmax_mode, void* stream, const AdapterAttnArgs* aa) {
+    FusedAttnCall c{};
+    c.qkv = qkv, c.B = 1, c.rope_cos = rope_cos, c.rope_sin = rope_sin, c.n_elem = n_elem, c.pos = pos;
+    c.n_groups = n_groups, c.q_per_kv = q_per_kv, c.hs = hs, c.S = S, c.nsplit = nsplit;
+    c.workspace = workspace, c.tickets = tickets, c.k_cache = k_cache, c.v_cache = v_cache, c.y = y;
+    c.softmax_mode = softmax_mode, c.st = (hipStream_t)stream;
+    return fused_attn_call("attn_fused_decode", c, FusedKind::OneRow, aa);
+}
+
+// prefix K/V, gate and aT of the two adapter entry points
+static int check_adapter_attn(const char* who, const void* ak, const void* av, const void* gate, int aT, int n_groups, int q_per_kv,
+                              int hs, AdapterAttnArgs* aa) {
+    PARROT_REQUIRE(ak && av && gate, "%s: null adapter pointer", who);
+    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && aT >= 1, "%s: bad shape n_groups=%d q_per_kv=%d aT=%d", who, n_groups, q_per_kv, aT);
+    PARROT_UNSUPPORTED(aT <= kAdapterMaxT, "%s: adapter_prompt_length %d > %d is not built (one prefix key per lane)", who, aT, kAdapterMaxT);
+    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
+    PARROT_REQUIRE(aligned16(ak) && aligned16(av) && (reinterpret_cast<uintptr_t>(gate) & 1u) == 0, "%s: ak / av must be 16-byte aligned", who);
+    *aa = AdapterAttnArgs{(const bf16_t*)ak, (const bf16_t*)av, (const bf16_t*)gate, aT};
+    return PARROT_OK;
 }
 
 }  // namespace parrot
@@ -1269,162 +1341,14 @@ int parrot_tune_attn_stamps(void* dbg8_u64) {  // diagnostic build: device buffe
 }
 #endif
 
-// softmax_mode 1 needs the whole window in one key block of the reference's kernel: one split, at most 512 slots
-static int check_softmax_mode(const char* who, int softmax_mode, int S, int nsplit) {
-    PARROT_REQUIRE(softmax_mode == 0 || softmax_mode == 1, "%s: softmax_mode must be 0 or 1", who);
-    PARROT_UNSUPPORTED(softmax_mode == 0 || (nsplit == 1 && S <= 512),
-                       "%s: softmax_mode 1 (the reference's bf16 probabilities) is built for one split and windows up to 512 slots (S=%d nsplit=%d)", who, S, nsplit);
-    return PARROT_OK;
-}
-
-static int attn_fused_entry(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
-                            int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
-                            void* k_cache, void* v_cache, void* y, int softmax_mode, const AdapterAttnArgs* aa, void* stream) {
-    {
-        const int rc = check_softmax_mode("attn_fused_decode", softmax_mode, S, nsplit);
-        if (rc != PARROT_OK) return rc;
-    }
-    PARROT_REQUIRE(qkv && pos && k_cache && v_cache && y, "attn_fused_decode: null pointer");
-    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1, "attn_fused_decode: bad shape");
-    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "attn_fused_decode: at most %d query heads per group (got %d)", kFusedMaxQ, q_per_kv);
-    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "attn_fused_decode: bad n_elem=%d", n_elem);
-    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "attn_fused_decode: rope tables missing");
-    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "attn_fused_decode: nsplit out of range");
-    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "attn_fused_decode: workspace and tickets required when nsplit > 1");
-    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "attn_fused_decode: 16-byte alignment");
-    hipStream_t st = (hipStream_t)stream;
-#define PARROT_FUSED_HS(HSV)                                                                                                      \
-    case HSV:                                                                                                                     \
-        if (aa)                                                                                                                   \
-            return attn_fused_launch<HSV, true>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, \
-                                                workspace, tickets, y, softmax_mode, st, *aa);                                     \
-        return attn_fused_launch<HSV>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, \
-                                      tickets, y, softmax_mode, st);
-    switch (hs) {
-        PARROT_FUSED_HS(32)
-        PARROT_FUSED_HS(64)
-        PARROT_FUSED_HS(128)
-        default: break;
-    }
-#undef PARROT_FUSED_HS
-    set_error("attn_fused_decode: head size %d not built (32, 64, 128)", hs);
-    return PARROT_EUNSUPPORTED;
-}
-
 int parrot_attn_fused_decode(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
                              int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
                              void* k_cache, void* v_cache, void* y, int softmax_mode, void* stream) {
-    return attn_fused_entry(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache,
-                            v_cache, y, softmax_mode, nullptr, stream);
+    return one_row_call(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache, v_cache, y,
+                        softmax_mode, stream, nullptr);
 }
 
-}  // extern "C"
-
-// the batched entry point and, with SEQ, the consecutive-rows one (`who` names the caller in the messages)
-template <bool SEQ>
-static int attn_fused_rows_entry(const char* who, const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
-                                 const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
-                                 void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
-                                 int softmax_mode, void* stream) {
-    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "%s: B=%d (1 .. %d)", who, B, kMaxDecodeRows);
-    {
-        const int rc = check_softmax_mode(who, softmax_mode, S, nsplit);
-        if (rc != PARROT_OK) return rc;
-    }
-    PARROT_REQUIRE(qkv && pos && k_cache && v_cache && y, "%s: null pointer", who);
-    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1, "%s: bad shape", who);
-    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "%s: at most %d query heads per group (got %d)", who, kFusedMaxQ, q_per_kv);
-    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
-    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "%s: bad n_elem=%d", who, n_elem);
-    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "%s: rope tables missing", who);
-    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "%s: nsplit out of range", who);
-    const int n_head = n_groups * q_per_kv;
-    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "%s: workspace and tickets required when nsplit > 1", who);
-    PARROT_REQUIRE(!tickets || n_tickets >= B * n_head, "%s: %d tickets, B * n_head = %d needed", who, n_tickets, B * n_head);
-    PARROT_REQUIRE(ldqkv >= n_groups * (q_per_kv + 2) * hs && ldqkv % 8 == 0, "%s: ldqkv=%d too small or not a multiple of 8", who, ldqkv);
-    PARROT_REQUIRE(ldy >= n_head * hs, "%s: ldy=%d too small", who, ldy);
-    PARROT_REQUIRE(SEQ || (kv_bstride >= (int64_t)n_groups * S * hs && kv_bstride % 8 == 0),
-                   "%s: kv_bstride=%lld below n_groups * S * hs or not a multiple of 8", who, (long long)kv_bstride);
-    PARROT_REQUIRE(!SEQ || B <= S, "%s: M=%d rows do not fit a cache of %d slots", who, B, S);
-    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache), "%s: 16-byte alignment", who);
-    const AttnRowsArgs rows{ldqkv, ldy, kv_bstride};
-    hipStream_t st = (hipStream_t)stream;
-    switch (hs) {
-        case 32: return attn_fused_launch<32, false, true, SEQ>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
-                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
-        case 64: return attn_fused_launch<64, false, true, SEQ>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
-                                                           nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
-        default: return attn_fused_launch<128, false, true, SEQ>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S,
-                                                            nsplit, workspace, tickets, y, softmax_mode, st, {}, B, rows);
-    }
-}
-
-extern "C" {
-
-int parrot_attn_fused_decode_rows(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
-                                  const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
-                                  void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
-                                  int softmax_mode, void* stream) {
-    return attn_fused_rows_entry<false>("attn_fused_decode_rows", qkv, ldqkv, B, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S,
-                                        nsplit, workspace, tickets, n_tickets, k_cache, v_cache, kv_bstride, y, ldy, softmax_mode, stream);
-}
-
-int parrot_attn_fused_decode_seq(const void* qkv, int ldqkv, int M, const void* rope_cos, const void* rope_sin, int n_elem,
-                                 const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
-                                 void* tickets, int n_tickets, void* k_cache, void* v_cache, void* y, int ldy, int softmax_mode,
-                                 void* stream) {
-    return attn_fused_rows_entry<true>("attn_fused_decode_seq", qkv, ldqkv, M, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S,
-                                       nsplit, workspace, tickets, n_tickets, k_cache, v_cache, 0, y, ldy, softmax_mode, stream);
-}
-
-int parrot_attn_fused_decode_prefix(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
-                                    const int32_t* pos, const int32_t* prefix_len, int n_groups, int q_per_kv, int hs, int S, int nsplit,
-                                    void* workspace, void* tickets, int n_tickets, const void* k_cache, const void* v_cache, void* k_tail,
-                                    void* v_tail, int S_tail, void* y, int ldy, int share_loads, int softmax_mode, void* stream) {
-    const char* who = "attn_fused_decode_prefix";
-    PARROT_REQUIRE(B >= 1 && B <= kMaxDecodeRows, "%s: B=%d (1 .. %d)", who, B, kMaxDecodeRows);
-    {
-        const int rc = check_softmax_mode(who, softmax_mode, S, nsplit);
-        if (rc != PARROT_OK) return rc;
-    }
-    PARROT_REQUIRE(qkv && pos && prefix_len && k_cache && v_cache && k_tail && v_tail && y, "%s: null pointer", who);
-    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && S >= 1 && S_tail >= 1, "%s: bad shape (S=%d S_tail=%d)", who, S, S_tail);
-    PARROT_UNSUPPORTED(q_per_kv <= kFusedMaxQ, "%s: at most %d query heads per group (got %d)", who, kFusedMaxQ, q_per_kv);
-    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
-    PARROT_REQUIRE(n_elem % 2 == 0 && n_elem >= 0 && n_elem <= hs, "%s: bad n_elem=%d", who, n_elem);
-    PARROT_REQUIRE(n_elem == 0 || (rope_cos && rope_sin), "%s: rope tables missing", who);
-    PARROT_REQUIRE(nsplit >= 1 && nsplit <= 65535, "%s: nsplit out of range", who);
-    const int n_head = n_groups * q_per_kv;
-    PARROT_REQUIRE(nsplit == 1 || (workspace && tickets), "%s: workspace and tickets required when nsplit > 1", who);
-    PARROT_REQUIRE(!tickets || n_tickets >= B * n_head, "%s: %d tickets, B * n_head = %d needed", who, n_tickets, B * n_head);
-    PARROT_REQUIRE(ldqkv >= n_groups * (q_per_kv + 2) * hs && ldqkv % 8 == 0, "%s: ldqkv=%d too small or not a multiple of 8", who, ldqkv);
-    PARROT_REQUIRE(ldy >= n_head * hs, "%s: ldy=%d too small", who, ldy);
-    PARROT_REQUIRE(aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache) && aligned16(k_tail) && aligned16(v_tail),
-                   "%s: 16-byte alignment", who);
-    const AttnPrefixArgs pa{ldqkv, ldy, (bf16_t*)k_tail, (bf16_t*)v_tail, prefix_len, S_tail, B, share_loads};
-    hipStream_t st = (hipStream_t)stream;
-    switch (hs) {
-        case 32: return attn_prefix_launch<32>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace,
-                                               tickets, y, softmax_mode, st, B, pa);
-        case 64: return attn_prefix_launch<64>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace,
-                                               tickets, y, softmax_mode, st, B, pa);
-        default: return attn_prefix_launch<128>(qkv, rope_cos, rope_sin, n_elem, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace,
-                                                tickets, y, softmax_mode, st, B, pa);
-    }
-}
-
-// prefix K/V, gate and aT of the two adapter entry points
-static int check_adapter_attn(const char* who, const void* ak, const void* av, const void* gate, int aT, int n_groups, int q_per_kv,
-                              int hs, AdapterAttnArgs* aa) {
-    PARROT_REQUIRE(ak && av && gate, "%s: null adapter pointer", who);
-    PARROT_REQUIRE(n_groups >= 1 && q_per_kv >= 1 && aT >= 1, "%s: bad shape n_groups=%d q_per_kv=%d aT=%d", who, n_groups, q_per_kv, aT);
-    PARROT_UNSUPPORTED(aT <= kAdapterMaxT, "%s: adapter_prompt_length %d > %d is not built (one prefix key per lane)", who, aT, kAdapterMaxT);
-    PARROT_UNSUPPORTED(hs == 32 || hs == 64 || hs == 128, "%s: head size %d not built (32, 64, 128)", who, hs);
-    PARROT_REQUIRE(aligned16(ak) && aligned16(av) && (reinterpret_cast<uintptr_t>(gate) & 1u) == 0, "%s: ak / av must be 16-byte aligned", who);
-    *aa = AdapterAttnArgs{(const bf16_t*)ak, (const bf16_t*)av, (const bf16_t*)gate, aT};
-    return PARROT_OK;
-}
-
+// (the one-row call behind the adapter's own checks: what both share is reported under the one-row name)
 int parrot_attn_fused_decode_adapter(const void* qkv, const void* rope_cos, const void* rope_sin, int n_elem, const int32_t* pos,
                                      int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace, void* tickets,
                                      void* k_cache, void* v_cache, void* y, const void* ak, const void* av, const void* gate, int aT,
@@ -1432,8 +1356,47 @@ int parrot_attn_fused_decode_adapter(const void* qkv, const void* rope_cos, cons
     AdapterAttnArgs aa;
     const int rc = check_adapter_attn("attn_fused_decode_adapter", ak, av, gate, aT, n_groups, q_per_kv, hs, &aa);
     if (rc != PARROT_OK) return rc;
-    return attn_fused_entry(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache,
-                            v_cache, y, softmax_mode, &aa, stream);
+    return one_row_call(qkv, rope_cos, rope_sin, n_elem, pos, n_groups, q_per_kv, hs, S, nsplit, workspace, tickets, k_cache, v_cache, y,
+                        softmax_mode, stream, &aa);
+}
+
+int parrot_attn_fused_decode_rows(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                  const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                  void* tickets, int n_tickets, void* k_cache, void* v_cache, int64_t kv_bstride, void* y, int ldy,
+                                  int softmax_mode, void* stream) {
+    FusedAttnCall c{};
+    c.qkv = qkv, c.ldqkv = ldqkv, c.B = B, c.rope_cos = rope_cos, c.rope_sin = rope_sin, c.n_elem = n_elem, c.pos = pos;
+    c.n_groups = n_groups, c.q_per_kv = q_per_kv, c.hs = hs, c.S = S, c.nsplit = nsplit;
+    c.workspace = workspace, c.tickets = tickets, c.n_tickets = n_tickets, c.k_cache = k_cache, c.v_cache = v_cache;
+    c.y = y, c.ldy = ldy, c.softmax_mode = softmax_mode, c.st = (hipStream_t)stream;
+    c.kv_bstride = kv_bstride;
+    return fused_attn_call("attn_fused_decode_rows", c, FusedKind::Rows);
+}
+
+int parrot_attn_fused_decode_seq(const void* qkv, int ldqkv, int M, const void* rope_cos, const void* rope_sin, int n_elem,
+                                 const int32_t* pos, int n_groups, int q_per_kv, int hs, int S, int nsplit, void* workspace,
+                                 void* tickets, int n_tickets, void* k_cache, void* v_cache, void* y, int ldy, int softmax_mode,
+                                 void* stream) {
+    FusedAttnCall c{};
+    c.qkv = qkv, c.ldqkv = ldqkv, c.B = M, c.rope_cos = rope_cos, c.rope_sin = rope_sin, c.n_elem = n_elem, c.pos = pos;
+    c.n_groups = n_groups, c.q_per_kv = q_per_kv, c.hs = hs, c.S = S, c.nsplit = nsplit;
+    c.workspace = workspace, c.tickets = tickets, c.n_tickets = n_tickets, c.k_cache = k_cache, c.v_cache = v_cache;
+    c.y = y, c.ldy = ldy, c.softmax_mode = softmax_mode, c.st = (hipStream_t)stream;
+    return fused_attn_call("attn_fused_decode_seq", c, FusedKind::Seq);
+}
+
+int parrot_attn_fused_decode_prefix(const void* qkv, int ldqkv, int B, const void* rope_cos, const void* rope_sin, int n_elem,
+                                    const int32_t* pos, const int32_t* prefix_len, int n_groups, int q_per_kv, int hs, int S, int nsplit,
+                                    void* workspace, void* tickets, int n_tickets, const void* k_cache, const void* v_cache, void* k_tail,
+                                    void* v_tail, int S_tail, void* y, int ldy, int share_loads, int softmax_mode, void* stream) {
+    FusedAttnCall c{};
+    c.qkv = qkv, c.ldqkv = ldqkv, c.B = B, c.rope_cos = rope_cos, c.rope_sin = rope_sin, c.n_elem = n_elem, c.pos = pos;
+    c.n_groups = n_groups, c.q_per_kv = q_per_kv, c.hs = hs, c.S = S, c.nsplit = nsplit;
+    c.workspace = workspace, c.tickets = tickets, c.n_tickets = n_tickets, c.k_cache = const_cast<void*>(k_cache), c.v_cache = const_cast<void*>(v_cache);
+    c.y = y, c.ldy = ldy, c.softmax_mode = softmax_mode, c.st = (hipStream_t)stream;
+    // (the shared cache is only read: attn_prefix_decode_kernel takes it as const)
+    c.prefix_len = prefix_len, c.k_tail = k_tail, c.v_tail = v_tail, c.S_tail = S_tail, c.share_loads = share_loads;
+    return fused_attn_call("attn_fused_decode_prefix", c, FusedKind::Prefix);
 }
 
 int parrot_attn_adapter_prefix(const void* q, int M, const void* ak, const void* av, const void* gate, int aT, int n_groups,
@@ -1447,13 +1410,10 @@ int parrot_attn_adapter_prefix(const void* q, int M, const void* ak, const void*
     PARROT_REQUIRE(ldy >= n_groups * q_per_kv * hs, "attn_adapter_prefix: ldy too small");
     PARROT_REQUIRE(aligned16(q), "attn_adapter_prefix: q must be 16-byte aligned");
     const int n_head = n_groups * q_per_kv;
-    const dim3 grid(n_head, M);
-    hipStream_t st = (hipStream_t)stream;
-    switch (hs) {
-        case 32: return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<32>, grid, dim3(64), 0, st, (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
-        case 64: return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<64>, grid, dim3(64), 0, st, (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
-        default: return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<128>, grid, dim3(64), 0, st, (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
-    }
+    return with_head_size("attn_adapter_prefix", hs, [&](auto HS) {
+        return launch(K_ATTN_ADAPTER_PREFIX, attn_adapter_prefix_kernel<decltype(HS)::value>, dim3(n_head, M), dim3(64), 0, (hipStream_t)stream,
+                      (const bf16_t*)q, n_head, aa, q_per_kv, (bf16_t*)y, ldy, softmax_mode);
+    });
 }
 
 int64_t parrot_attn_workspace_floats(int M, int n_head, int hs, int nsplit) {
@@ -1472,15 +1432,10 @@ int parrot_attn_decode(const void* q, int M, const int32_t* pos, const void* k_c
     PARROT_REQUIRE(nsplit == 1 || workspace, "attn_decode: workspace required when nsplit > 1");
     PARROT_REQUIRE(ldy >= n_groups * q_per_kv * hs, "attn_decode: ldy too small");
     PARROT_REQUIRE(aligned16(q) && aligned16(k_cache) && aligned16(v_cache), "attn_decode: q/k/v must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    switch (hs) {
-        case 32: return attn_launch<32>(q, M, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, y, ldy, softmax_mode, st);
-        case 64: return attn_launch<64>(q, M, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, y, ldy, softmax_mode, st);
-        case 128: return attn_launch<128>(q, M, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, y, ldy, softmax_mode, st);
-        default: break;
-    }
-    set_error("attn_decode: head size %d not built (32, 64, 128)", hs);
-    return PARROT_EUNSUPPORTED;
+    return with_head_size("attn_decode", hs, [&](auto HS) {
+        return attn_launch<decltype(HS)::value>(q, M, pos, k_cache, v_cache, n_groups, q_per_kv, S, nsplit, workspace, y, ldy, softmax_mode,
+                                                (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

@@ -251,29 +251,6 @@ __device__ __forceinline__ float row8_allsum(float v) {
     }
     return v;
 }
-// attention: sum over the LPR lanes of a key row / all-reduce over the key rows of a piece (as attn.hip)
-template <int LPR>
-__device__ __forceinline__ float eng_group_sum(float v) {
-    v += dpp0<0xB1>(v);
-    v += dpp0<0x4E>(v);
-    if (LPR >= 8) v += dpp0<0x141>(v);
-    if (LPR >= 16) v += dpp0<0x128>(v);
-    return v;
-}
-template <int LPR, bool MAX>
-__device__ __forceinline__ float eng_slot_allreduce(float v) {
-    auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : a + b; };
-    if (LPR <= 8) v = op(v, dpp0<0x128>(v));
-    {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    }
-    {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    }
-    return v;
-}
 
 // what every wave of the workgroup knows
 struct EngCtx {
@@ -1322,7 +1299,7 @@ __device__ __forceinline__ bool eng_attn_local(const EngState& st, const EngCtx&
                 s = fmaf(qf[h][2 * e], bflo(kd[e]), s);
                 s = fmaf(qf[h][2 * e + 1], bfhi(kd[e]), s);
             }
-            s = eng_group_sum<LPR>(s);
+            s = group_sum<LPR>(s);
             if (ok) {
                 const float mn = fmaxf(m[h], s);
                 const float corr = __expf(m[h] - mn), pp = __expf(s - mn);
@@ -1342,13 +1319,13 @@ __device__ __forceinline__ bool eng_attn_local(const EngState& st, const EngCtx&
     // ---- merge the key rows of the wave, then the waves of the CU
 #pragma unroll
     for (int h = 0; h < HQ; ++h) {
-        const float M = eng_slot_allreduce<LPR, true>(m[h]);
+        const float M = slot_allreduce<LPR, true>(m[h]);
         const float f = (m[h] == -INFINITY) ? 0.f : __expf(m[h] - M);
-        const float L = eng_slot_allreduce<LPR, false>(l[h] * f);
+        const float L = slot_allreduce<LPR, false>(l[h] * f);
         float* wp = wpart + (w.cw * HQ + h) * PW;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float a = eng_slot_allreduce<LPR, false>(acc[h][e] * f);
+            const float a = slot_allreduce<LPR, false>(acc[h][e] * f);
             if (c.lane < LPR) wp[dl * 8 + e] = a;
         }
         if (c.lane == 0) {

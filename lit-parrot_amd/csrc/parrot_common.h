@@ -236,6 +236,35 @@ __device__ __forceinline__ float wave_sum_order8(float v) {
     v += dpp0<0x4E>(v);   // quad_perm [2,3,0,1]
     return v;
 }
+// decode attention (attn.hip, engine.hip): sum over the LPR lanes that share a key row (LPR = 4, 8 or 16 consecutive lanes); every lane of the group gets the
+// total.  DPP only: no LDS crossbar (ds_bpermute) and no lgkmcnt waits in the key loop's dependent chain.
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {
+    v += dpp0<0xB1>(v);                    // quad_perm [1,0,3,2]
+    v += dpp0<0x4E>(v);                    // quad_perm [2,3,0,1]
+    if (LPR >= 8) v += dpp0<0x141>(v);     // row_half_mirror: the two quads of an 8-lane group
+    if (LPR >= 16) v += dpp0<0x128>(v);    // row_ror:8: the two halves of a 16-lane row
+    return v;
+}
+
+// all-reduce over the 64 / LPR row slots of a wave (lanes with the same lane % LPR): DPP rotations inside the 16-lane rows,
+// then the gfx950 lane swaps across rows (v_permlane16_swap / v_permlane32_swap with both operands the same register
+// return the two halves, which are then combined) - no ds_bpermute.
+template <int LPR, bool MAX>
+__device__ __forceinline__ float slot_allreduce(float v) {
+    auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : a + b; };
+    if (LPR <= 4) v = op(v, dpp0<0x124>(v));  // row_ror:4
+    if (LPR <= 8) v = op(v, dpp0<0x128>(v));  // row_ror:8 - every lane now holds its 16-lane row's result
+    {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));  // rows 0+1 and 2+3
+    }
+    {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));  // both halves
+    }
+    return v;
+}
 __device__ __forceinline__ int wave_sum_i32_to_lane63(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
     v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);

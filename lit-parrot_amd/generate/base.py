@@ -28,7 +28,7 @@ import torch
 
 from .. import ops
 from .._hip import ParrotHipError
-from ..model import GPT
+from ..model import GPT, Rows
 
 
 @contextlib.contextmanager
@@ -80,11 +80,8 @@ def _run_prompt(model: GPT, tokens: torch.Tensor, T: int, zero_pos: torch.Tensor
     """``tokens[:T]`` through the multi-row path (M = T rows) into ``caches`` (one ``(k, v)`` of (n_groups, S, hs) per layer);
     returns the last row's logits (1, V).  ``zero_pos``: an int32[1] on the device that holds 0."""
     ws = model.workspace(T, tokens.device, 1)
-    ws.pos_is_zero = True  # the prompt starts at position 0: its attention may take the MFMA kernel (no ring wrap in the call)
-    try:
-        return model.run_rows(ws, tokens, None, zero_pos, S, caches, model.rope_cache)
-    finally:
-        ws.pos_is_zero = False
+    # the prompt starts at position 0: its attention may take the MFMA kernel (no ring wrap in the call)
+    return model.run_rows(ws, tokens, None, zero_pos, S, caches, model.rope_cache, pos_is_zero=True)
 
 
 def _capture(step: Callable[[], object], written: Sequence[torch.Tensor], device: torch.device, draws_rng: bool) -> "torch.cuda.CUDAGraph":
@@ -322,12 +319,12 @@ class BatchDecodeSession(_Session):
     def __init__(self, model: GPT, B: int, max_seq_length: int, max_tokens: int, greedy: bool,
                  sampler: Optional[Tuple[float, Optional[int]]] = None, eos_id: int = -1, use_graph: bool = True) -> None:
         self._open_rows("generate_batch", model, B, max_seq_length, max_tokens + 1, B, greedy, sampler, eos_id, use_graph,
-                        rows_are_sequences=True)
+                        Rows.SEQUENCES)
         self.caches = list(model.kv_caches)  # (B, n_groups, S, hs) per layer
         self._drop_reference_weights()
 
     def _open_rows(self, fn: str, model: GPT, B: int, max_seq_length: int, length: int, kv_batch: int, greedy: bool,
-                   sampler: Optional[Tuple[float, Optional[int]]], eos_id: int, use_graph: bool, **rows) -> None:
+                   sampler: Optional[Tuple[float, Optional[int]]], eos_id: int, use_graph: bool, rows: Rows) -> None:
         """The buffers of a step over B rows, each with a token buffer of ``length``; ``rows``: what the rows are to the workspace."""
         self._open(fn, model, max_seq_length, (B, length), kv_batch, use_graph)
         self.B, self.greedy, self.eos_id = B, greedy, eos_id
@@ -336,7 +333,7 @@ class BatchDecodeSession(_Session):
         self.pos = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.end = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.ws = model.workspace(B, dev, B, **rows)
+        self.ws = model.workspace(B, dev, B, rows)
         V = model.config.padded_vocab_size
         self.first_logits = torch.empty((B, V), dtype=torch.bfloat16, device=dev)  # the prompts' last rows
         self.noise = torch.empty((B, V), dtype=torch.bfloat16, device=dev) if self.sampler is not None else None
@@ -488,7 +485,7 @@ class CandidateSession(BatchDecodeSession):
                  sampler: Optional[Tuple[float, Optional[int]]] = None, eos_id: int = -1, use_graph: bool = True) -> None:
         # (no position reaches the window's end: the token buffer is as long as the window)
         self._open_rows("generate_candidates", model, n, max_seq_length, max_seq_length + 1, 1, greedy, sampler, eos_id, use_graph,
-                        rows_share_prefix=True)
+                        Rows.SHARED_PREFIX)
         self.S_tail = tail_slots
         dev, c = self.device, model.config
         self.prefix_len = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -613,7 +610,7 @@ class SpeculativeSession(_Session):
         self.end = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.state = torch.zeros((ops.SPEC_STATE_WORDS,), dtype=torch.int32, device=dev)
         self.ws_one = model.workspace(1, dev, 1)
-        self.ws_rows = model.workspace(self.M, dev, self.M, rows_are_drafts=True)
+        self.ws_rows = model.workspace(self.M, dev, self.M, Rows.DRAFTS)
         self.graphs: Dict[bool, torch.cuda.CUDAGraph] = {}  # True: the M-row step, False: the one-row step
         self.caches = [(k[0], v[0]) for k, v in model.kv_caches]
         self._drop_reference_weights()

@@ -22,6 +22,7 @@ Deliberate differences from the reference (documented in DESIGN.md): the KV cach
 ``max_seq_length`` the cache is used as a ring (slot = pos % S) instead of being rolled left (:238-242) — the same
 window of keys, in a different slot order; ``input_pos`` must be consecutive positions.
 """
+import enum
 import math
 import os
 from typing import Any, List, Optional, Tuple
@@ -47,27 +48,31 @@ def norm_class(config: Config):
     return RMSNorm if config._norm_class == "RMSNorm" else nn.LayerNorm
 
 
+class Rows(enum.Enum):
+    """What the ``M`` rows of a ``Workspace`` are.
+
+    ``CONSECUTIVE``: positions ``pos .. pos + M - 1`` of one sequence - a prompt, or the one new token.
+    ``SEQUENCES``: batched decode - row b is the one new token of sequence b (its own position and KV cache).
+    ``SHARED_PREFIX``: candidates - as ``SEQUENCES``, but the rows continue ONE prompt; the caches handed to ``run_rows`` are
+    ``ops.PrefixCache`` pairs (the prompt's K/V once, a tail per row) and the attention is ``ops.attn_fused_decode_prefix``.
+    ``DRAFTS``: speculative decode - positions as ``CONSECUTIVE``, but every row must come out bit for bit as the one-row step
+    computes it: its attention is the fused decode kernel's (``ops.attn_fused_decode_seq``), not the prompt kernels'."""
+    # (the values are the last word of ``GPT.workspace``'s cache key; tests find the batched workspace by its "rows")
+    CONSECUTIVE = "consecutive"
+    SEQUENCES = "rows"
+    SHARED_PREFIX = "prefix"
+    DRAFTS = "drafts"
+
+
 class Workspace:
-    """Every intermediate of ``M`` token rows through the network (allocated once per M).
+    """Every intermediate of ``M`` token rows through the network (allocated once per M and ``Rows`` mode)."""
 
-    ``rows_are_sequences``: batched decode - row b is the one new token of sequence b (its own position and KV cache), not
-    position ``pos + b`` of one sequence.
-    ``rows_are_drafts``: speculative decode - the rows are positions ``pos .. pos + M - 1`` of one sequence, as in a prompt, but
-    every row must come out bit for bit as the one-row step computes it: its attention is the fused decode kernel's
-    (``ops.attn_fused_decode_seq``), not the prompt kernels'.
-    ``rows_share_prefix`` (implies ``rows_are_sequences``): candidates - the rows continue ONE prompt; the caches handed to
-    ``run_rows`` are ``ops.PrefixCache`` pairs (the prompt's K/V once, a tail per row) and the attention is
-    ``ops.attn_fused_decode_prefix``."""
-
-    def __init__(self, config: Config, M: int, device, lm_rows: int, rows_are_sequences: bool = False,
-                 rows_are_drafts: bool = False, rows_share_prefix: bool = False) -> None:
-        def buf(cols: int, rows: int = M) -> torch.Tensor:
-            return torch.empty((rows, cols), dtype=torch.bfloat16, device=device)
+    def __init__(self, config: Config, M: int, device, lm_rows: int, rows: Rows = Rows.CONSECUTIVE) -> None:
+        def buf(cols: int, n: int = M) -> torch.Tensor:
+            return torch.empty((n, cols), dtype=torch.bfloat16, device=device)
 
         c = config
-        rows_are_sequences = rows_are_sequences or rows_share_prefix
-        self.M, self.lm_rows, self.rows_are_sequences, self.rows_are_drafts = M, lm_rows, rows_are_sequences, rows_are_drafts
-        self.rows_share_prefix = rows_share_prefix
+        self.M, self.lm_rows, self.rows = M, lm_rows, rows
         self.x, self.t = buf(c.n_embd), buf(c.n_embd)
         self.qkv = buf(c.qkv_size)
         self.q = buf(c.n_head * c.head_size)
@@ -77,7 +82,7 @@ class Workspace:
         self.zero_pos = torch.zeros((1,), dtype=torch.int32, device=device)
         self.side_stream = None  # parallel-residual blocks: the MLP's first Linear runs beside the attention branch
         # fused attention arrival counters (n_head per sequence / per draft row)
-        self.tickets = torch.zeros((M * c.n_head if rows_are_sequences or rows_are_drafts else c.n_head,), dtype=torch.int32, device=device)
+        self.tickets = torch.zeros((c.n_head if rows is Rows.CONSECUTIVE else M * c.n_head,), dtype=torch.int32, device=device)
         self._attn_ws = {}
 
     def attn_ws(self, config: Config, nsplit: int) -> torch.Tensor:
@@ -212,25 +217,22 @@ class GPT(nn.Module):
             for _ in range(c.n_layer)
         ]
 
-    def workspace(self, M: int, device, lm_rows: Optional[int] = None, rows_are_sequences: bool = False,
-                  rows_are_drafts: bool = False, rows_share_prefix: bool = False) -> Workspace:
+    def workspace(self, M: int, device, lm_rows: Optional[int] = None, rows: Rows = Rows.CONSECUTIVE) -> Workspace:
         lm_rows = M if lm_rows is None else lm_rows
-        rows_are_sequences = rows_are_sequences or rows_share_prefix
-        key = ((M, lm_rows, str(device)) + (("rows",) if rows_are_sequences else ()) + (("drafts",) if rows_are_drafts else ())
-               + (("prefix",) if rows_share_prefix else ()))
+        key = (M, lm_rows, str(device), rows.value)
         if key not in self._workspaces:
             if len(self._workspaces) > 8:
                 self._workspaces.clear()
-            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows_are_sequences, rows_are_drafts, rows_share_prefix)
+            self._workspaces[key] = Workspace(self.config, M, device, lm_rows, rows)
         return self._workspaces[key]
 
     def batched_decode_unsupported(self) -> Optional[str]:
-        """Why the batched decode step (one row per sequence, ``Workspace(rows_are_sequences=True)``) cannot run this model,
+        """Why the batched decode step (one row per sequence, ``Rows.SEQUENCES``) cannot run this model,
         or None when it can."""
         return self._rows_decode_unsupported()
 
     def speculative_decode_unsupported(self) -> Optional[str]:
-        """Why the speculative decode step (``Workspace(rows_are_drafts=True)``: a token and its drafts as the rows of one pass, each
+        """Why the speculative decode step (``Rows.DRAFTS``: a token and its drafts as the rows of one pass, each
         row bit for bit the one-row step) cannot run this model, or None when it can."""
         return self._rows_decode_unsupported()
 
@@ -252,26 +254,29 @@ class GPT(nn.Module):
 
     # ------------------------------------------------------------------------------------------ execution
     def run_rows(self, ws: Workspace, tokens: torch.Tensor, tok_pos: Optional[torch.Tensor], pos: torch.Tensor,
-                 S: int, caches: List[KVCache], rope: RoPECache, *, rope_local: bool = False) -> torch.Tensor:
+                 S: int, caches: List[KVCache], rope: RoPECache, *, rope_local: bool = False,
+                 pos_is_zero: bool = False) -> torch.Tensor:
         """Embed ``ws.M`` tokens (``tokens[tok_pos + m]``), run every block, final norm and lm_head.
 
         ``pos`` (device int32[1]) is the position of row 0; ``caches[i]`` are (n_groups, S, hs) views.  Returns
         ``ws.logits``: all rows, or only the last row when the workspace was built with ``lm_rows == 1``.
-        Batched decode (``ws.rows_are_sequences``): row b embeds ``tokens[b, tok_pos[b]]`` (``tokens[b, 0]`` without tok_pos)
+        ``pos_is_zero``: the caller knows that ``pos`` holds 0 (a prompt from the start: no ring wrap inside the call), so the
+        attention of a long prompt may take the MFMA kernel.
+        Batched decode (``Rows.SEQUENCES``): row b embeds ``tokens[b, tok_pos[b]]`` (``tokens[b, 0]`` without tok_pos)
         at position ``pos[b]`` (int32[M]); ``caches[i]`` are the (M, n_groups, S, hs) caches of the M sequences, or, with
-        ``ws.rows_share_prefix``, the ``ops.PrefixCache`` pair of the layer (``S`` is the shared cache's window).
-        Speculative decode (``ws.rows_are_drafts``): the arguments of a prompt; the caller keeps ``pos + M`` inside the window.
+        ``Rows.SHARED_PREFIX``, the ``ops.PrefixCache`` pair of the layer (``S`` is the shared cache's window).
+        Speculative decode (``Rows.DRAFTS``): the arguments of a prompt; the caller keeps ``pos + M`` inside the window.
         """
         M = ws.M
-        if ws.rows_are_sequences:
+        if ws.rows in (Rows.SEQUENCES, Rows.SHARED_PREFIX):
             ops.embedding_rows(self.transformer.wte.weight.data, tokens, tok_pos, ws.x)
             nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, 1)  # each row splits as one sequence does
         else:
             ops.embedding(self.transformer.wte.weight.data, tokens, tok_pos, M, ws.x)
             # (draft rows split as the one-row step does: the same partial sums in the same order)
-            nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, 1 if ws.rows_are_drafts else M)
+            nsplit = ops.attn_nsplit(self.config.n_query_groups, S, self.config.q_per_kv, 1 if ws.rows is Rows.DRAFTS else M)
         for block, (kc, vc) in zip(self.transformer.h, caches):
-            block.run_rows(ws, pos, S, kc, vc, rope, nsplit, rope_local)
+            block.run_rows(ws, pos, S, kc, vc, rope, nsplit, rope_local, pos_is_zero)
         last = ws.x if ws.lm_rows == M else ws.x[M - 1:M]
         logits = _linear(self.lm_head, last, ws.logits, norm=self.transformer.ln_f)  # ln_f fused into lm_head
         return logits
@@ -307,7 +312,7 @@ class GPT(nn.Module):
         if (use_kv_cache and T == 1 and 2 <= B <= ops.GEMV_MAX_ROWS and ops.BATCHED_DECODE
                 and self.batched_decode_unsupported() is None):
             # one batched pass: row b is sequence b at the shared position (the reference's one input_pos), in cache slice b
-            ws = self.workspace(B, idx.device, B, rows_are_sequences=True)
+            ws = self.workspace(B, idx.device, B, Rows.SEQUENCES)
             logits = self.run_rows(ws, idx, None, pos.expand(B).contiguous(), S, self.kv_caches, self.rope_cache)
             return logits.view(B, 1, -1).clone()
         ws = self.workspace(T, idx.device)
@@ -320,9 +325,9 @@ class GPT(nn.Module):
                 caches = [tuple(torch.empty((c.n_query_groups, S, c.head_size), dtype=torch.bfloat16, device=idx.device)
                                 for _ in range(2))] * 1
                 caches = caches * c.n_layer  # the same scratch pair serves every layer in turn
-            ws.pos_is_zero = not use_kv_cache  # without a cache the rows are positions 0 .. T-1; with one, input_pos lives on the device
-            logits = self.run_rows(ws, idx[b], None, pos if pos is not None else ws.zero_pos, S, caches, self.rope_cache)
-            ws.pos_is_zero = False
+            # without a cache the rows are positions 0 .. T-1; with one, input_pos lives on the device
+            logits = self.run_rows(ws, idx[b], None, pos if pos is not None else ws.zero_pos, S, caches, self.rope_cache,
+                                   pos_is_zero=not use_kv_cache)
             out[b].copy_(logits)
         return out
 
@@ -338,7 +343,7 @@ class Block(nn.Module):
         self.config = config
 
     def run_rows(self, ws: Workspace, pos: torch.Tensor, S: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                 rope: RoPECache, nsplit: int, rope_local: bool = False) -> None:
+                 rope: RoPECache, nsplit: int, rope_local: bool = False, pos_is_zero: bool = False) -> None:
         """One block over ``ws.x`` in place (reference Block.forward, model.py:158-180)."""
         c = self.config
         # norm_1 is fused into the QKV linear, norm_2 into the MLP's first linear: no normalised copy is materialised
@@ -355,12 +360,12 @@ class Block(nn.Module):
                 ws.side_stream.wait_stream(main)  # x of this block is final
                 with torch.cuda.stream(ws.side_stream):
                     self.mlp.run_up(ws, ws.x, norm=mlp_norm)  # -> ws.h
-                self.attn.run_rows(ws, ws.x, pos, S, k_cache, v_cache, rope, nsplit, rope_local, norm=self.norm_1)
+                self.attn.run_rows(ws, ws.x, pos, S, k_cache, v_cache, rope, nsplit, rope_local, norm=self.norm_1, pos_is_zero=pos_is_zero)
                 _linear(self.attn.proj, ws.y, ws.t, epilogue=EPI_RESIDUAL, residual=ws.x)
                 main.wait_stream(ws.side_stream)
                 self.mlp.run_down(ws, residual=ws.t, out=ws.x)
                 return
-            self.attn.run_rows(ws, ws.x, pos, S, k_cache, v_cache, rope, nsplit, rope_local, norm=self.norm_1)  # -> ws.y
+            self.attn.run_rows(ws, ws.x, pos, S, k_cache, v_cache, rope, nsplit, rope_local, norm=self.norm_1, pos_is_zero=pos_is_zero)  # -> ws.y
             _linear(self.attn.proj, ws.y, ws.t, epilogue=EPI_RESIDUAL, residual=ws.x)
             self.mlp.run_rows(ws, ws.x, residual=ws.t, out=ws.x, norm=mlp_norm)
         else:
@@ -369,7 +374,7 @@ class Block(nn.Module):
                     "No checkpoint amongst the ones we support uses this configuration"
                     " (non-parallel residual and shared attention norm)."
                 )
-            self.attn.run_rows(ws, ws.x, pos, S, k_cache, v_cache, rope, nsplit, rope_local, norm=self.norm_1)  # -> ws.y
+            self.attn.run_rows(ws, ws.x, pos, S, k_cache, v_cache, rope, nsplit, rope_local, norm=self.norm_1, pos_is_zero=pos_is_zero)  # -> ws.y
             _linear(self.attn.proj, ws.y, ws.x, epilogue=EPI_RESIDUAL, residual=ws.x)  # x = x + h
             self.mlp.run_rows(ws, ws.x, residual=ws.x, out=ws.x, norm=self.norm_2)  # x = x + mlp(norm_2(x))
 
@@ -408,37 +413,35 @@ class CausalSelfAttention(nn.Module):
 
     def run_rows(self, ws: Workspace, x: torch.Tensor, pos: torch.Tensor, S: int, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, rope: RoPECache, nsplit: int, rope_local: bool = False,
-                 norm: Optional[nn.Module] = None) -> torch.Tensor:
+                 norm: Optional[nn.Module] = None, pos_is_zero: bool = False) -> torch.Tensor:
         """(norm +) qkv linear, split + RoPE + cache append, attention over the cache; leaves the heads in ``ws.y``
         (the output projection is fused with the residual add by the caller).  A single new token takes the fused
         kernel (one launch); several rows (prefill) take rope_kvappend + attn_decode over all rows."""
         c = self.config
         _linear(self.attn, x, ws.qkv, norm=norm)
         prefix = self.adapter_prefix()
-        if ws.rows_are_sequences:  # batched decode: one row per sequence, every row in one launch
-            if prefix is not None:
-                raise ParrotHipError("the batched decode step has no adapter-prefix term: adapter models decode one sequence at a time")
-            if ws.rows_share_prefix:  # candidates: one shared prompt cache, a tail per row
-                return ops.attn_fused_decode_prefix(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,
-                                                    c.q_per_kv, c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
-            return ops.attn_fused_decode_rows(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv,
-                                              c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
-        if ws.rows_are_drafts:  # speculative decode: append the K/V rows of all rows, then every row through the fused decode kernel
-            if prefix is not None or rope_local:
-                raise ParrotHipError("the speculative decode step has no adapter-prefix term and takes absolute positions")
-            ops.rope_kvappend(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, c.n_query_groups, c.q_per_kv, c.head_size, S,
-                              ws.q, k_cache, v_cache, False)
-            return ops.attn_fused_decode_seq(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv,
-                                             c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
-        if ws.M == 1 and not rope_local and c.q_per_kv <= ops.FUSED_ATTN_MAX_Q_PER_KV:
+        mode = ws.rows
+        if mode in (Rows.SEQUENCES, Rows.SHARED_PREFIX) and prefix is not None:
+            raise ParrotHipError("the batched decode step has no adapter-prefix term: adapter models decode one sequence at a time")
+        if mode is Rows.DRAFTS and (prefix is not None or rope_local):
+            raise ParrotHipError("the speculative decode step has no adapter-prefix term and takes absolute positions")
+        if mode is not Rows.CONSECUTIVE or (ws.M == 1 and not rope_local and c.q_per_kv <= ops.FUSED_ATTN_MAX_Q_PER_KV):
+            call = (ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups, c.q_per_kv, c.head_size, S,
+                    nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
+            if mode is Rows.SEQUENCES:  # batched decode: one row per sequence
+                return ops.attn_fused_decode_rows(*call)
+            if mode is Rows.SHARED_PREFIX:  # candidates: one shared prompt cache, a tail per row
+                return ops.attn_fused_decode_prefix(*call)
+            if mode is Rows.DRAFTS:  # speculative decode: append the K/V rows of all rows, then every row through the fused decode kernel
+                ops.rope_kvappend(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, c.n_query_groups, c.q_per_kv, c.head_size, S,
+                                  ws.q, k_cache, v_cache, False)
+                return ops.attn_fused_decode_seq(*call)
             if prefix is not None:  # LLaMA-Adapter layer (adapter.py): the gated prefix term inside the same launch
-                return ops.attn_fused_decode_adapter(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,
-                                                     c.q_per_kv, c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y, prefix)
-            return ops.attn_fused_decode(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, k_cache, v_cache, c.n_query_groups,
-                                         c.q_per_kv, c.head_size, S, nsplit, ws.attn_ws(c, nsplit), ws.tickets, ws.y)
+                return ops.attn_fused_decode_adapter(*call, prefix)
+            return ops.attn_fused_decode(*call)
         ops.rope_kvappend(ws.qkv, rope[0], rope[1], c.rope_n_elem, pos, c.n_query_groups, c.q_per_kv, c.head_size, S,
                           ws.q, k_cache, v_cache, rope_local)
-        y = self._attend_rows(ws, pos, S, k_cache, v_cache, nsplit)
+        y = self._attend_rows(ws, pos, S, k_cache, v_cache, nsplit, pos_is_zero)
         if prefix is not None:
             ops.attn_adapter_prefix(ws.q, c.n_query_groups, c.q_per_kv, c.head_size, y, prefix)
         return y
@@ -448,9 +451,9 @@ class CausalSelfAttention(nn.Module):
         return None
 
     def _attend_rows(self, ws: Workspace, pos: torch.Tensor, S: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                     nsplit: int) -> torch.Tensor:
+                     nsplit: int, pos_is_zero: bool = False) -> torch.Tensor:
         c = self.config
-        if (ATTN_PREFILL_MFMA and getattr(ws, "pos_is_zero", False) and ops.ATTN_PREFILL_MIN_ROWS <= ws.M <= S
+        if (ATTN_PREFILL_MFMA and pos_is_zero and ops.ATTN_PREFILL_MIN_ROWS <= ws.M <= S
                 and c.head_size in (32, 64, 128)):
             # a prompt that starts at position 0 (no ring wrap inside the call): flash attention on the matrix cores
             n = c.n_query_groups * c.head_size * ((S + 63) // 64 * 64)

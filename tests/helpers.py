@@ -28,3 +28,10 @@ def assert_bf16_close(got: torch.Tensor, want: torch.Tensor, ulps: int = 1, atol
 def rbf(t: torch.Tensor) -> torch.Tensor:
     """round to bf16 precision, keep float64/float32 container"""
     return t.to(torch.bfloat16).to(t.dtype)
+
+
+# Which instantiation the fused decode attention launches is picked from the head size, the query heads per K/V group (1, 2, a partly
+# filled pass of 4, two passes), the keys per split (windows of 32 and 192 slots lie on both sides of the 16-wave rule at one split
+# for every head size) and the softmax mode (1: one split only).  Every entry point is run over this grid once, n_groups = 2.
+ATTN_PICK_SHAPES = [(hs, q_per_kv) for hs in (32, 64, 128) for q_per_kv in (1, 2, 3, 8)]
+ATTN_PICK_WINDOWS = [(S, nsplit, mode) for S in (32, 192) for nsplit, mode in ((1, 0), (1, 1), (2, 0))]

@@ -6,6 +6,8 @@ prompts of any length whose tail fits; the prompt prefilled and stored once (lau
 import pytest
 import torch
 
+from helpers import ATTN_PICK_SHAPES, ATTN_PICK_WINDOWS
+
 pytestmark = pytest.mark.gpu
 
 import lit_parrot_amd as L  # noqa: E402
@@ -62,6 +64,19 @@ def test_attn_prefix_equals_the_rows_kernel(n_groups, q_per_kv, hs, n_elem, S, n
     """attn_fused_decode_prefix == attn_fused_decode_rows on B caches cat(prefix[:, :T], tail[b][:, :S - T]): y and the appended
     row bit for bit, every other tail slot and the shared cache untouched, the tickets re-armed; called twice, the second time one
     position further.  Row positions are spread over [T, S - 1] and include pos = T."""
+    prefix_equals_the_rows_kernel(n_groups, q_per_kv, hs, n_elem, S, nsplit, mode, Ts, B, share)
+
+
+@pytest.mark.parametrize("hs,q_per_kv", ATTN_PICK_SHAPES)
+@pytest.mark.parametrize("S,nsplit,mode", ATTN_PICK_WINDOWS)
+@pytest.mark.parametrize("share", [True, False])
+def test_attn_prefix_equals_the_rows_kernel_over_the_pick_grid(hs, q_per_kv, S, nsplit, mode, share, share_switch):
+    """The same at every point of the launch's pick grid (helpers.ATTN_PICK_*), three rows; T = 1, the border of the two splits and
+    three slots past it (with ``share`` the first split then goes to the shared-load launch)."""
+    prefix_equals_the_rows_kernel(2, q_per_kv, hs, hs, S, nsplit, mode, (1, S // 2, S // 2 + 3), 3, share)
+
+
+def prefix_equals_the_rows_kernel(n_groups, q_per_kv, hs, n_elem, S, nsplit, mode, Ts, B, share):
     g = gen(31 + B)
     n_head, width = n_groups * q_per_kv, n_groups * (q_per_kv + 2) * hs
     cos, sin = (t.to(DEV) for t in om.rope_tables(1024, n_elem, BF, math_dtype=BF))

@@ -12,7 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import assert_bf16_close, rbf
+from helpers import ATTN_PICK_SHAPES, ATTN_PICK_WINDOWS, assert_bf16_close, rbf
 
 pytestmark = pytest.mark.gpu
 
@@ -679,6 +679,50 @@ def test_softmax_mode_1_is_the_reference_kernels_arithmetic(n_groups, q_per_kv, 
         big = torch.zeros((n_groups, 513, hs), dtype=BF, device=DEV)
         with pytest.raises(ParrotHipError, match="softmax_mode 1"):
             ops.attn_decode(q, pos_d, big, big, n_groups, q_per_kv, hs, 513, 1, ws, y1)
+    finally:
+        ops.ATTN_SOFTMAX_MODE = 0
+
+
+@pytest.mark.parametrize("hs,q_per_kv", ATTN_PICK_SHAPES)
+@pytest.mark.parametrize("S,nsplit,mode", ATTN_PICK_WINDOWS)
+def test_fused_decode_attention_over_the_pick_grid(hs, q_per_kv, S, nsplit, mode):
+    """parrot_attn_fused_decode at every point of its launch's pick grid (helpers.ATTN_PICK_*) against float64 on the same bf16
+    inputs, at position 0, mid-window and past the window (the ring wraps): the appended K/V row bit for bit (ref_attention's RoPE),
+    the heads within the bound of the tests above.  softmax_mode 1 against its restated arithmetic (bf16 probabilities, see
+    test_softmax_mode_1_is_the_reference_kernels_arithmetic)."""
+    n_groups, n_elem = 2, hs
+    g = gen(23)
+    n_head, width = n_groups * q_per_kv, n_groups * (q_per_kv + 2) * hs
+    cos, sin = om.rope_tables(512, n_elem, BF, math_dtype=BF)
+    cos_d, sin_d = cos.to(DEV), sin.to(DEV)
+    tickets = torch.zeros((n_head,), dtype=torch.int32, device=DEV)
+    y = torch.empty((1, n_head * hs), dtype=BF, device=DEV)
+    ops.ATTN_SOFTMAX_MODE = mode
+    try:
+        ws = ops.attn_workspace(1, n_head, hs, nsplit, DEV)
+        kc = torch.randn((n_groups, S, hs), generator=g).to(BF)
+        vc = torch.randn((n_groups, S, hs), generator=g).to(BF)
+        kc_d, vc_d = kc.to(DEV), vc.to(DEV)
+        for pos in (0, S // 2, S + 5):
+            qkv = torch.randn(1, width, generator=g).to(BF)
+            one_k, one_v = (torch.zeros((n_groups, pos + 1, hs), dtype=BF) for _ in range(2))
+            qr, _ = ref_attention(qkv, cos, sin, pos, n_groups, q_per_kv, hs, n_elem, pos + 1, one_k, one_v)  # the roped row at slot pos
+            kc[:, pos % S], vc[:, pos % S] = one_k[:, pos], one_v[:, pos]
+            ops.attn_fused_decode(qkv.to(DEV), cos_d, sin_d, n_elem, torch.tensor([pos], dtype=torch.int32, device=DEV), kc_d, vc_d,
+                                  n_groups, q_per_kv, hs, S, nsplit, ws, tickets, y)
+            what = f"pos={pos}"
+            assert torch.equal(kc_d.cpu(), kc) and torch.equal(vc_d.cpu(), vc), f"{what}: K/V caches differ"
+            n = min(pos + 1, S)
+            K, V = kc[:, :n].double(), vc[:, :n].double()
+            if mode == 0:
+                att = torch.einsum("gqd,gsd->gqs", qr[:, :, 0].double(), K) / math.sqrt(hs)
+                want = torch.einsum("gqs,gsd->gqd", att.softmax(-1), V)
+            else:
+                sc = torch.einsum("gqd,gsd->gqs", qr[:, :, 0].double(), K).float() * (1.0 / math.sqrt(hs))
+                p = torch.exp(sc - sc.amax(dim=-1, keepdim=True))
+                want = torch.einsum("gqs,gsd->gqd", p.to(BF).double(), V) / p.double().sum(-1, keepdim=True)
+            assert_bf16_close(y.view(-1), want.reshape(-1), ulps=1, atol=2e-3, what=what)
+            assert int(tickets.abs().sum()) == 0, f"{what}: arrival tickets must be re-armed"
     finally:
         ops.ATTN_SOFTMAX_MODE = 0
 

@@ -274,7 +274,7 @@ def test_prompt_pass_every_row(name, mode):
 def test_prompt_in_two_calls(name, mode, mfma):
     """A prompt processed in two multi-row calls (driven as CandidateSession.prefill drives ``run_rows``): the second call's rows
     start at pos0 = 37 behind the first call's keys, where the needle its last row asks for lies.  ``mfma``: the second call through
-    the matrix-core kernel (the workspace flag that says the call does not wrap the ring), else through the row-by-row kernel."""
+    the matrix-core kernel (the ``run_rows`` argument that says the call does not wrap the ring), else through the row-by-row kernel."""
     cfg, _, ids, oracle, _ = family(name)
     model = gpu_model(name, mode)
     T1, T2, S = 37, 200, 300
@@ -287,12 +287,8 @@ def test_prompt_in_two_calls(name, mode, mfma):
         sess.pos.zero_()
         for T0, M in ((0, T1), (T1, T2)):
             ws = model.workspace(M, DEV, 1)
-            ws.pos_is_zero = T0 == 0 or mfma
             sess.pos.fill_(T0)
-            try:
-                logits = model.run_rows(ws, sess.tokens, sess.pos, sess.pos, S, sess.caches, model.rope_cache)
-            finally:
-                ws.pos_is_zero = False
+            logits = model.run_rows(ws, sess.tokens, sess.pos, sess.pos, S, sess.caches, model.rope_cache, pos_is_zero=T0 == 0 or mfma)
         one = rm.Scenario(tokens=sc.tokens[: sc.T], T=sc.T, S=S)
         check(name, mode, ids, one, logits.view(1, -1), ref, f"two calls, needle at {slot}, mfma={mfma}")
     model.reset_cache()

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import ATTN_PICK_SHAPES, ATTN_PICK_WINDOWS
+
 pytestmark = pytest.mark.gpu
 
 import lit_parrot_amd as L  # noqa: E402
@@ -225,6 +227,17 @@ ATTN = [(4, 1, 64, 64), (2, 4, 128, 128), (1, 16, 64, 32), (2, 3, 128, 64)]  # t
 def test_attn_seq_equals_sequential_one_row_calls(n_groups, q_per_kv, hs, n_elem, S, nsplit, mode, M):
     """rope_kvappend + attn_fused_decode_seq over M rows == M attn_fused_decode calls on copies of the caches: y and every K/V
     slot bit for bit, at position 0, mid-window and up to the last slot, called twice (the tickets re-arm)."""
+    seq_equals_sequential_one_row_calls(n_groups, q_per_kv, hs, n_elem, S, nsplit, mode, M)
+
+
+@pytest.mark.parametrize("hs,q_per_kv", ATTN_PICK_SHAPES)
+@pytest.mark.parametrize("S,nsplit,mode", ATTN_PICK_WINDOWS)
+def test_attn_seq_equals_sequential_one_row_calls_over_the_pick_grid(hs, q_per_kv, S, nsplit, mode):
+    """The same at every point of the launch's pick grid (helpers.ATTN_PICK_*), three rows."""
+    seq_equals_sequential_one_row_calls(2, q_per_kv, hs, hs, S, nsplit, mode, 3)
+
+
+def seq_equals_sequential_one_row_calls(n_groups, q_per_kv, hs, n_elem, S, nsplit, mode, M):
     g = gen(77 + M)
     n_head, width = n_groups * q_per_kv, n_groups * (q_per_kv + 2) * hs
     cos, sin = (t.to(DEV) for t in om.rope_tables(1024, n_elem, BF, math_dtype=BF))
