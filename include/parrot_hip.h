@@ -340,6 +340,25 @@ int parrot_ngram_draft(int64_t* tokens, int L, const int32_t* pos, int draft_len
 int parrot_verify_advance(const void* logits, int V, int ldl, int M, int64_t* tokens, int L, int32_t* pos, const int32_t* end,
                           int eos_id, int32_t* state, int32_t* row_pos, void* stream);
 
+/* ---- scoring: the log-probability of a GIVEN token ---------------------------------------------------------
+ * For a row x of V bf16 logits and a token t, in fp32 with expf / logf: mx = max_i x_i, lse = mx + log(sum_i exp(x_i - mx)),
+ * logprob = x_t - lse; is_greedy = 1 iff t is the token parrot_argmax_advance would emit for the row (the maximum, the lowest
+ * index on ties; a NaN logit counts as -inf there).  A NaN logit makes the row's logprob NaN.  t outside [0, V): logprob = NaN,
+ * is_greedy = 0, and nothing is read for it.  One workgroup per row; the row is read once (held in registers) when every row is
+ * 16-byte aligned, V % 8 == 0 and V <= 65536, else element by element.
+ *
+ * parrot_token_logprob_rows: row m of logits [M][ldl] against targets[m] (int64[M]) -> logprob[m] (float[M]) and, unless
+ * NULL, is_greedy[m] (int32[M]): the rows of a prompt pass.
+ *
+ * parrot_logprob_advance_rows: the teacher-forced twin of parrot_argmax_advance_rows, 1 <= B <= 8.  Row b with p = pos[b] is
+ * frozen when p + 1 >= min(end[b], ldt, ldo): it writes nothing and does not advance.  A live row scores the token that is
+ * already at tokens[b][p + 1] (int64 [B][ldt], never written) against logits[b] into logprob[b][p + 1] and is_greedy[b][p + 1]
+ * (float / int32 [B][ldo]: the column is the token's position), then pos[b] = p + 1.                                          */
+int parrot_token_logprob_rows(const void* logits, int V, int ldl, int M, const int64_t* targets, float* logprob, int32_t* is_greedy,
+                              void* stream);
+int parrot_logprob_advance_rows(const void* logits, int V, int ldl, int B, const int64_t* tokens, int ldt, int32_t* pos,
+                                const int32_t* end, float* logprob, int32_t* is_greedy, int ldo, void* stream);
+
 /* ---- stream engine: ONE launch per decode token ------------------------------------------------------------
  * The whole token (generate/base.py:131-153 for one iteration: embedding, every Block of lit_gpt/model.py:158-180,
  * ln_f, lm_head, greedy sampling) runs as one launch of 256 workgroups, one per CU (csrc/engine.hip).  In every

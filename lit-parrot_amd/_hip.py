@@ -125,6 +125,8 @@ SIGNATURES = {
     "parrot_topk_sample_rows": (_i, [_vp, _i, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "parrot_ngram_draft": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "parrot_verify_advance": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "parrot_token_logprob_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "parrot_logprob_advance_rows": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -34,7 +34,8 @@ static const char* const kNames[K_COUNT] = {
     "attn_combine", "embedding",    "argmax_advance", "w4_gemm", "bf16_gemm", "attn_fused_decode", "eng_token", "e4_repack", "stop_check", "gptq_block",
     "w4c_gemv", "w4c_gemv_dual", "w4c_dequant", "gemm_xsum", "gemm_splitk_epilogue", "w4c_gemm", "attn_prefill_vt", "attn_prefill", "w8_gemm", "w8_dequant_epilogue", "w8_outlier", "topk_sample",
     "adapter_epilogue", "attn_adapter_prefix", "embedding_rows", "argmax_advance_rows", "topk_sample_rows", "attn_fused_decode_rows",
-    "attn_fused_decode_seq", "ngram_draft", "verify_advance", "attn_fused_decode_prefix"};
+    "attn_fused_decode_seq", "ngram_draft", "verify_advance", "attn_fused_decode_prefix",
+    "token_logprob_rows", "logprob_advance_rows"};
 
 }  // namespace parrot
 

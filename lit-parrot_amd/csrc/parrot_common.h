@@ -106,6 +106,8 @@ enum KernelId : int {
     K_NGRAM_DRAFT,
     K_VERIFY_ADVANCE,
     K_ATTN_FUSED_PREFIX,
+    K_TOKEN_LOGPROB_ROWS,
+    K_LOGPROB_ADVANCE_ROWS,
     K_COUNT
 };
 

@@ -113,7 +113,7 @@ def _capture(step: Callable[[], object], written: Sequence[torch.Tensor], device
 
 
 class _Session:
-    """The construction and the capture the four sessions share.  A session adds its buffers, ``_step`` (the launch sequence that
+    """The construction and the capture the sessions share.  A session adds its buffers, ``_step`` (the launch sequence that
     gets captured) and, where the step writes something else than tokens, pos and the K/V caches, ``_written``."""
 
     def _open(self, fn: str, model: GPT, max_seq_length: int, tokens_shape: Tuple[int, ...], kv_batch: int, use_graph: bool) -> None:
@@ -562,6 +562,47 @@ def generate_candidates(
     sess = _cached_session(model, key, max_returned_tokens, lambda: CandidateSession(model, n, max_seq_length, tail, greedy, sampler, eos))
     sess.prefill(idx.to(device=sess.device, dtype=torch.int64), max_returned_tokens)
     return _decode_rows(sess, [idx] * n, max_returned_tokens, eos_id)
+
+
+class ScoringSession(CandidateSession):
+    """CandidateSession with the tokens GIVEN: n rows (1 <= n <= 8) that continue ONE prompt with known continuations, scored.
+
+        tokens      int64[n][L]     row b: the prompt, then continuation b, written ahead of time and never by the step
+        end         int32[n]        T + len_b: row b freezes once its last token is scored
+        logprob     float32[n][L]   column p: log P(tokens[b, p] | tokens[b, :p]) for T <= p < end[b]
+        is_greedy   int32[n][L]     column p: whether tokens[b, p] is the arg-max of that row of logits
+
+    The step is the candidates step with ``ops.logprob_advance_rows`` in the place of the sampling launch (score.py)."""
+
+    def __init__(self, model: GPT, n: int, max_seq_length: int, tail_slots: int, use_graph: bool = True) -> None:
+        super().__init__(model, n, max_seq_length, tail_slots, True, use_graph=use_graph)
+        self.logprob = torch.zeros(self.tokens.shape, dtype=torch.float32, device=self.device)
+        self.is_greedy = torch.zeros(self.tokens.shape, dtype=torch.int32, device=self.device)
+
+    def sample(self, logits: torch.Tensor, eos_id: int = -1) -> None:
+        """Row b: the token at ``tokens[b, pos[b] + 1]`` scored against ``logits[b]``, ``pos[b] += 1``, unless the row is at its end."""
+        ops.logprob_advance_rows(logits, self.tokens, self.pos, self.end, self.logprob, self.is_greedy)
+
+    def _written(self) -> List[torch.Tensor]:
+        return super()._written() + [self.logprob, self.is_greedy]
+
+    def prefill(self, prompt: torch.Tensor, continuations: Sequence[torch.Tensor]) -> None:
+        """The prompt ONCE into the shared cache (CandidateSession.prefill) and every continuation behind it in its row."""
+        T = self.T = prompt.numel()
+        for b, c in enumerate(continuations):
+            self.tokens[b, T:T + c.numel()].copy_(c)
+        super().prefill(prompt, 0)
+        self.end.copy_(torch.tensor([T + c.numel() for c in continuations], dtype=torch.int32))
+
+    def score_first(self) -> None:
+        """Entry 0 of every row from the prompt's last-row logits, in one ``token_logprob_rows`` launch; leaves ``pos`` = T."""
+        T = self.T
+        first = torch.empty((self.B,), dtype=torch.float32, device=self.device)
+        greedy = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        ops.token_logprob_rows(self.first_logits, self.tokens[:, T].contiguous(), first, greedy)
+        self.logprob[:, T] = first
+        self.is_greedy[:, T] = greedy
+        self.pos.fill_(T)
 
 
 # ------------------------------------------------------------------------------------------------ speculative decode

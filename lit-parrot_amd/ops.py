@@ -667,3 +667,36 @@ def stop_check(tokens: torch.Tensor, pos: torch.Tensor, first_gen: torch.Tensor,
         raise ParrotHipError("stop_check: tokens / stop_flat int64; pos, first_gen, stop_off, flag int32")
     check(_hip.load().parrot_stop_check(ptr(tokens), ptr(pos), ptr(first_gen), ptr(stop_flat), ptr(stop_off), n_stop, longest,
                                         ptr(flag), stream()), "parrot_stop_check")
+
+
+# ---- scoring (score.py; generate/base.py::ScoringSession)
+def token_logprob_rows(logits: torch.Tensor, targets: torch.Tensor, logprob: torch.Tensor, is_greedy: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``logprob[m]`` = log_softmax(logits[m])[targets[m]] in fp32 for the M rows of ``logits`` (M, V) - one launch, no fp32 copy of
+    the logits - and, when given, ``is_greedy[m]`` = whether ``targets[m]`` is the row's arg-max (argmax_advance's tie rule).  A
+    target outside [0, V) scores NaN."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ParrotHipError("token_logprob_rows: logits must be bf16 rows (M, V)")
+    M = logits.shape[0]
+    if targets.dtype != torch.int64 or targets.numel() != M or not targets.is_contiguous():
+        raise ParrotHipError(f"token_logprob_rows: targets must be a contiguous int64 vector of M = {M} tokens")
+    if logprob.dtype != torch.float32 or logprob.numel() != M or not logprob.is_contiguous():
+        raise ParrotHipError(f"token_logprob_rows: logprob must be a contiguous float32 vector of M = {M} entries")
+    if is_greedy is not None and (is_greedy.dtype != torch.int32 or is_greedy.numel() != M or not is_greedy.is_contiguous()):
+        raise ParrotHipError(f"token_logprob_rows: is_greedy must be a contiguous int32 vector of M = {M} entries")
+    check(_hip.load().parrot_token_logprob_rows(ptr(logits), logits.shape[1], logits.stride(0), M, ptr(targets), ptr(logprob),
+                                                ptr(is_greedy), stream()), "parrot_token_logprob_rows")
+    return logprob
+
+
+def logprob_advance_rows(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, end: torch.Tensor, logprob: torch.Tensor,
+                         is_greedy: torch.Tensor) -> None:
+    """Teacher-forced batched step: per row b, the token already at ``tokens[b, pos[b] + 1]`` is scored against ``logits[b]`` into
+    ``logprob[b, pos[b] + 1]`` / ``is_greedy[b, pos[b] + 1]`` and ``pos[b] += 1`` - unless the row is frozen (next position at
+    ``end[b]``).  ``tokens`` is never written."""
+    B = _sample_rows_args("logprob_advance_rows", logits, tokens, pos, end)
+    for t, nm, dt in ((logprob, "logprob", torch.float32), (is_greedy, "is_greedy", torch.int32)):
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] != B or t.stride(1) != 1 or t.stride(0) != logprob.stride(0):
+            raise ParrotHipError(f"logprob_advance_rows: {nm} must be {dt} rows (B, L) with one leading dimension for both outputs")
+    check(_hip.load().parrot_logprob_advance_rows(ptr(logits), logits.shape[1], logits.stride(0), B, ptr(tokens), tokens.stride(0),
+                                                  ptr(pos), ptr(end), ptr(logprob), ptr(is_greedy), logprob.stride(0), stream()),
+          "parrot_logprob_advance_rows")
