@@ -6,9 +6,11 @@ from .model import GPT, Block, CausalSelfAttention, GptNeoxMLP, LLaMAMLP, apply_
 from .rmsnorm import RMSNorm
 from .score import continuation_logprobs, perplexity, rank_continuations, score_windows, token_logprobs
 from .utils import quantization
+from .weights import weights_changed
 
 __all__ = [
     "GPT", "Block", "CausalSelfAttention", "GptNeoxMLP", "LLaMAMLP", "RMSNorm", "Config", "name_to_config",
     "generate", "generate_batch", "generate_candidates", "generate_speculative", "quantization", "apply_rope", "build_rope_cache", "ParrotHipError",
     "token_logprobs", "continuation_logprobs", "rank_continuations", "perplexity", "score_windows",
+    "weights_changed",
 ]

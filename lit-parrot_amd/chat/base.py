@@ -21,6 +21,7 @@ from .. import ops
 from .._hip import ParrotHipError
 from ..generate.base import DecodeSession
 from ..model import GPT
+from ..weights import weights_generation
 
 CHUNK = 8          # greedy: graph replays between two reads of the stop flag
 MAX_STOP_SEQS = 16
@@ -79,7 +80,8 @@ def _session(model: GPT, max_seq_length: int, max_tokens: int, greedy: bool, n_s
     key = (max_seq_length, greedy, n_stop, longest, sampler)
     sess = cache.get(key)
     stale = (sess is None or sess.tokens.numel() < max_tokens + 1 or not model.kv_caches
-             or model.kv_caches[0][0].data_ptr() != sess.caches[0][0].data_ptr())
+             or model.kv_caches[0][0].data_ptr() != sess.caches[0][0].data_ptr()
+             or sess.weights_generation != weights_generation(model))
     if stale:
         cache.pop(key, None)
         sess = None

@@ -142,9 +142,11 @@ def lazy_load(path: Union[str, Path]) -> Dict[str, torch.Tensor]:
 def stream_load(model: torch.nn.Module, state_dict: Dict[str, torch.Tensor]) -> List[str]:
     """Fill ``model`` (already on the HIP device, possibly built under ``quantization(...)``) from ``state_dict`` one tensor at
     a time.  Dense ``<linear>.weight`` entries going into int4 / int8 Linears are quantised on the device on the way in.
+    ``state_dict`` may hold any subset of the model's keys.  A model that has decoded before decodes with the new weights next.
     Returns the checkpoint keys that were not used."""
     from .quantize.bnb import InferenceLinear8bitLt, Linear4bit
     from .quantize.gptq import ColBlockQuantizedLinear, pack_nibbles, rtn_quantize
+    from .weights import weights_changed
 
     modules = dict(model.named_modules())
     for m in modules.values():  # (an int4 Linear whose reference-layout buffers a decode session released: resident again)
@@ -162,8 +164,6 @@ def stream_load(model: torch.nn.Module, state_dict: Dict[str, torch.Tensor]) -> 
             mod.scales.copy_(s)
             mod.zeros.copy_(z)
             mod.quant_weight.copy_(pack_nibbles(q))
-            mod._packed = None
-            mod.image_epoch += 1
             del w, q, s, z
         elif isinstance(mod, (InferenceLinear8bitLt, Linear4bit)) and leaf == "weight" and value.is_floating_point():
             mod._quantize_weight(value.to(mod.weight.device))
@@ -172,10 +172,11 @@ def stream_load(model: torch.nn.Module, state_dict: Dict[str, torch.Tensor]) -> 
             if tgt.shape != value.shape:
                 raise ValueError(f"{key}: checkpoint shape {tuple(value.shape)} != model shape {tuple(tgt.shape)}")
             tgt.data.copy_(value.to(device=tgt.device, dtype=tgt.dtype))
-            if isinstance(mod, ColBlockQuantizedLinear):
-                mod._packed = None
         else:
             unused.append(key)
+    # the copies above go through .data, which nothing can see: captured steps, engine images and every module's kernel-layout
+    # copy are dropped here, for a partial load too (weights.py)
+    weights_changed(model)
     return unused
 
 

@@ -17,6 +17,7 @@ from ._hip import (ENG_ATTN, ENG_EPI_LOGITS, ENG_GEMV, ENG_W_E4, ENG_W_E8, ENG_W
 from .quantize.bnb import InferenceLinear8bitLt
 from .quantize.gptq import ColBlockQuantizedLinear
 from .rmsnorm import RMSNorm
+from .weights import image_stamp, weights_generation
 
 
 def e4_image(lin: ColBlockQuantizedLinear, partner: Optional[ColBlockQuantizedLinear] = None, k0: int = 0,
@@ -257,8 +258,9 @@ class StreamEngine:
         # The kernel-layout images belong to the MODEL, not to the session: generate()'s caller resets the KV caches between
         # prompts (model.reset_cache(), generate/base.py:250 of the reference), the session and its engine are rebuilt, and a
         # rebuilt engine must not repack (and, for a moment, hold a second copy of) every weight.  Keyed by the Linear, its
-        # partner, the K-chunk and the state of the weights the image was built from.
+        # partner, the K-chunk and the state of the weights the image was built from (weights.image_stamp).
         model_images = model.__dict__.setdefault("_engine_images", {})
+        generation = weights_generation(model)
         images = {}
         self.kmax = 0
         chunks = self._down_chunks(c, wfmt)
@@ -293,12 +295,10 @@ class StreamEngine:
                 op.bias = ptr(lin.bias.data)
             img = images.get((id(lin), k0, k1))
             if img is None:
-                def stamp(m):  # what the image was built from: a later load / .to() / optimiser step moves it on
-                    return None if m is None else ((id(m), m.image_epoch) if e4 else (id(m), m.weight.data_ptr(), m.weight._version))
-                mkey = (stamp(lin), stamp(partner), k0, k1)
+                mkey = image_stamp(model, lin, partner, k0, k1, generation)
                 img = model_images.get(mkey)
                 if img is None:
-                    for old in [k for k in model_images if k[0][0] == id(lin) and k[2:] == (k0, k1)]:
+                    for old in [k for k in model_images if k[0][0] == id(lin) and k[2:4] == (k0, k1)]:
                         del model_images[old]  # an image of the same Linear from before its weights changed
                     if e8:
                         if (k0, k1) != (0, lin.in_features):

@@ -29,6 +29,7 @@ import torch
 from .. import ops
 from .._hip import ParrotHipError
 from ..model import GPT, Rows
+from ..weights import weights_generation
 
 
 @contextlib.contextmanager
@@ -120,6 +121,8 @@ class _Session:
         """The device (``fn``: the entry point an error names), the token buffer, the model's RoPE tables and its ``kv_caches``
         with batch ``kv_batch`` and a window of ``max_seq_length`` slots, rebuilt when they are anything else."""
         self.model, self.S, self.use_graph = model, max_seq_length, use_graph
+        # the state of the weights the session's buffers, images and captured launches belong to: stale under any other
+        self.weights_generation = weights_generation(model)
         self.device = _cuda_device(fn, model)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.tokens = torch.zeros(tokens_shape, dtype=torch.int64, device=self.device)
@@ -235,7 +238,7 @@ MAX_SESSIONS_PER_MODEL = 4  # captured steps kept per model (keyed by window, gr
 
 def _cached_session(model: GPT, key: Tuple, max_tokens: int, make: Callable):
     """The session under ``key`` in the model's LRU cache of captured steps (single-sequence and batched sessions alike), rebuilt
-    by ``make()`` when it is missing, too short, or no longer holds the model's current KV caches."""
+    by ``make()`` when it is missing, too short, no longer holds the model's current KV caches, or was built from other weights."""
     cache: Dict[Tuple, object] = model.__dict__.setdefault("_decode_sessions", {})
     sess = cache.get(key)
     stale = (
@@ -243,6 +246,7 @@ def _cached_session(model: GPT, key: Tuple, max_tokens: int, make: Callable):
         or sess.tokens.shape[-1] < max_tokens + 1
         or not model.kv_caches
         or model.kv_caches[0][0].data_ptr() != sess.caches[0][0].data_ptr()
+        or sess.weights_generation != weights_generation(model)
     )
     if stale:
         cache.pop(key, None)

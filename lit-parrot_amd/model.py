@@ -34,6 +34,7 @@ from . import ops
 from ._hip import EPI_GELU, EPI_NONE, EPI_RESIDUAL, EPI_SWIGLU, ParrotHipError
 from .config import Config
 from .rmsnorm import RMSNorm
+from .weights import weights_changed, weights_generation
 
 # parallel-residual blocks: overlap the MLP up-projection with the attention branch (M = 1); PARROT_PARALLEL_BRANCHES=0 disables
 PARALLEL_BRANCHES = os.environ.get("PARROT_PARALLEL_BRANCHES", "1") != "0"
@@ -193,6 +194,25 @@ class GPT(nn.Module):
 
     def reset_cache(self) -> None:
         self.kv_caches.clear()
+
+    # ------------------------------------------------------------------------------------------ derived state follows the weights
+    @property
+    def weights_generation(self) -> int:
+        """Moves on whenever the weights may have changed (weights.py); captured steps and engine images are valid for one value."""
+        return weights_generation(self)
+
+    def load_state_dict(self, *args, **kwargs):
+        try:
+            return super().load_state_dict(*args, **kwargs)
+        finally:  # (also when a strict load raises: the tensors it names have been copied by then)
+            weights_changed(self)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to() / .cpu() / .cuda() / .bfloat16(): every tensor may be a new one, and captured launches hold the old addresses
+        try:
+            return super()._apply(fn, *args, **kwargs)
+        finally:
+            weights_changed(self)
 
     # ------------------------------------------------------------------------------------------ caches
     def build_rope_cache(self, idx: torch.Tensor) -> RoPECache:

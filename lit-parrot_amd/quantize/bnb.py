@@ -13,6 +13,7 @@ import torch
 
 from .. import ops
 from .._hip import EPI_NONE, ParrotHipError
+from ..weights import next_epoch
 
 
 FUSED_DECODE = True  # single rows take parrot_w8_gemv_fused (tests switch it off to compare with the two-launch path)
@@ -29,7 +30,8 @@ class InferenceLinear8bitLt(torch.nn.Linear):
         if self.bias is not None:
             self.bias.requires_grad_(False)
         self._act: Optional[ops.W8Act] = None
-        self._pair = None  # (CB, SCB) of [self; partner] concatenated for the SwiGLU epilogue
+        self._pair = None  # (key, CB, SCB) of [self; partner] concatenated for the SwiGLU epilogue, see pair_with
+        self.image_epoch = next_epoch()  # moves on whenever the weight may have changed (weights.py: derived state is keyed by it)
         # the reference quantises the freshly initialised weight right away (bnb.py:34-36); that needs the GPU, so
         # here it happens when the module reaches the device (see _apply) or a checkpoint is loaded
 
@@ -55,6 +57,7 @@ class InferenceLinear8bitLt(torch.nn.Linear):
         setattr(self.weight, "CB", CB)
         setattr(self.weight, "SCB", SCB)
         self._pair = None
+        self.image_epoch = next_epoch()
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs) -> None:
         key = prefix + "weight"
@@ -71,14 +74,24 @@ class InferenceLinear8bitLt(torch.nn.Linear):
     def _apply(self, fn, *args, **kwargs):
         scb = getattr(self.weight, "SCB", None)
         out = super()._apply(fn, *args, **kwargs)
+        self._pair = None
+        self.image_epoch = next_epoch()
         if self.is_quantized and scb is not None:
             # nn.Module._apply may have rebuilt the Parameter: carry CB / SCB over, on the same device as CB
             setattr(self.weight, "CB", self.weight.data)
             setattr(self.weight, "SCB", scb.to(self.weight.device))
-            self._pair = None
         elif not self.is_quantized and self.weight.is_cuda:
             self._quantize_weight(self.weight.data)
         return out
+
+    def pair_with(self, partner: "InferenceLinear8bitLt"):
+        """(CB, SCB) of [self; partner] for the SwiGLU epilogue: built once per state of BOTH weights (a reload of fc_2 alone
+        must not leave fc_1 with the old half)."""
+        key = (self.image_epoch, id(partner), partner.image_epoch)
+        if self._pair is None or self._pair[0] != key:
+            self._pair = (key, torch.cat([self.weight.data, partner.weight.data]).contiguous(),
+                          torch.cat([self.weight.SCB, partner.weight.SCB]).contiguous())
+        return self._pair[1], self._pair[2]
 
     # -------------------------------------------------------------------------------------- HIP path
     def prep(self, x: torch.Tensor, norm=None) -> ops.W8Act:
@@ -94,9 +107,7 @@ class InferenceLinear8bitLt(torch.nn.Linear):
             raise ParrotHipError("InferenceLinear8bitLt: weight not quantised yet (move the module to the GPU)")
         CB, SCB = self.weight.data, self.weight.SCB
         if partner is not None:
-            if self._pair is None:
-                self._pair = (torch.cat([CB, partner.weight.data]).contiguous(), torch.cat([SCB, partner.weight.SCB]).contiguous())
-            CB, SCB = self._pair
+            CB, SCB = self.pair_with(partner)
         if act is None and x.shape[0] == 1 and self.in_features <= ops.W8_FUSED_MAX_K and FUSED_DECODE:
             # decode: activation quantiser (with the fused norm) + GEMV in one launch
             return ops.w8_linear_fused(CB, SCB, self.out_features, self.in_features, x, self.threshold, out, bias=self.bias,
@@ -252,6 +263,7 @@ class Linear4bit(torch.nn.Linear):
             self.bias.requires_grad_(False)
         self._packed = None  # W4K records (device)
         self._codes = None   # (bf16 codebook as int32 words, fp32 codebook) on the device
+        self.image_epoch = next_epoch()  # moves on whenever the weight may have changed (weights.py)
 
     @property
     def is_quantized(self) -> bool:
@@ -267,6 +279,7 @@ class Linear4bit(torch.nn.Linear):
         self.weight = torch.nn.Parameter(packed, requires_grad=False)
         setattr(self.weight, "quant_state", state)
         self._packed = None
+        self.image_epoch = next_epoch()
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs) -> None:
         key = prefix + "weight"
@@ -282,6 +295,7 @@ class Linear4bit(torch.nn.Linear):
         state = getattr(self.weight, "quant_state", None)
         out = super()._apply(fn, *args, **kwargs)
         self._packed = None
+        self.image_epoch = next_epoch()
         if self.is_quantized and state is not None:
             dev = self.weight.device
             moved = [t.to(dev) if torch.is_tensor(t) else t for t in state]

@@ -10,7 +10,8 @@ optional ``bias``), ``pack_weight`` / ``get_weight`` / ``forward``.  Differences
   * the kernel reads a repacked copy of the weights ("W4K") built once after loading.  A decode session
     (generate/base.py) then RELEASES the reference-layout buffers (``release_reference``): W4K is the one resident image
     of the weights, and ``state_dict()`` / ``get_weight()`` / a later ``.to()`` rebuild ``quant_weight`` / ``scales`` /
-    ``zeros`` from it with the exact inverse repack (bit for bit: tests/test_full_size_gpu.py).
+    ``zeros`` from it with the exact inverse repack (bit for bit: tests/test_full_size_gpu.py); so does reading one of the three
+    attributes, and assigning one counts as a change of the weights (``image_epoch``, weights.py).
 ``rtn_quantize`` is the round-to-nearest quantiser used for synthetic weights (find_params_weight semantics,
 gptq.py:317-347).
 """
@@ -20,6 +21,9 @@ import torch
 
 from .. import ops
 from .._hip import EPI_NONE, ParrotHipError
+from ..weights import next_epoch
+
+_REFERENCE_BUFFERS = ("quant_weight", "scales", "zeros")
 
 
 class ColBlockQuantizedLinear(torch.nn.Module):
@@ -42,13 +46,36 @@ class ColBlockQuantizedLinear(torch.nn.Module):
         self._packed: Optional[torch.Tensor] = None  # W4K copy (device), rebuilt when the buffers change
         self._released = False     # the reference-layout buffers are empty placeholders: W4K is the only image
         self._ref_dtype = None     # dtype of scales / zeros while released
-        self.image_epoch = 0       # moves on whenever the weights may have changed (derived images are keyed by it)
+        self.image_epoch = next_epoch()  # moves on whenever the weights may have changed (weights.py: derived state is keyed by it)
+
+    # The reference-interface buffers stay usable while a decode session has released them: reading one makes all three
+    # resident again, assigning one (``lin.scales = s``, the idiom of GPTQQuantizer.quantize and synth.py) does so first and
+    # then counts as a change of the weights.
+    def __getattr__(self, name: str):
+        if name in _REFERENCE_BUFFERS and self.__dict__.get("_released"):
+            self.restore_reference()
+        return super().__getattr__(name)
+
+    def __setattr__(self, name: str, value) -> None:
+        if name in _REFERENCE_BUFFERS and "image_epoch" in self.__dict__:
+            self.restore_reference()
+            super().__setattr__(name, value)
+            self._packed = None
+            self.image_epoch = next_epoch()
+            return
+        super().__setattr__(name, value)
+        if name == "bias" and "image_epoch" in self.__dict__:
+            self.image_epoch = next_epoch()  # (a captured step holds the old buffer's address)
+
+    def _set_reference(self, qw: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor) -> None:
+        """Swap the three buffers for other holders of the SAME weights (release / restore): no change of the weights."""
+        self._buffers["quant_weight"], self._buffers["scales"], self._buffers["zeros"] = qw, scales, zeros
 
     # -------------------------------------------------------------------------------------- format (torch ops)
     def pack_weight(self, weight: torch.Tensor) -> None:
         """Quantise ``weight`` (out, in) onto the grid given by ``scales``/``zeros`` and store the nibbles."""
         self.restore_reference()
-        self.image_epoch += 1
+        self.image_epoch = next_epoch()
         w = weight.to(device=self.quant_weight.device, dtype=torch.float32)
         g = torch.arange(self.in_features, device=w.device) // self.tile_cols
         q = torch.round(w / self.scales.float()[:, g] + self.zeros.float()[:, g]).clamp_(0, 15).to(torch.uint8)
@@ -78,9 +105,8 @@ class ColBlockQuantizedLinear(torch.nn.Module):
         self.packed()
         self._ref_dtype = self.scales.dtype
         dev = self.quant_weight.device
-        self.quant_weight = torch.empty((0,), dtype=torch.uint8, device=dev)
-        self.scales = torch.empty((0,), dtype=self._ref_dtype, device=dev)
-        self.zeros = torch.empty((0,), dtype=self._ref_dtype, device=dev)
+        self._set_reference(torch.empty((0,), dtype=torch.uint8, device=dev), torch.empty((0,), dtype=self._ref_dtype, device=dev),
+                            torch.empty((0,), dtype=self._ref_dtype, device=dev))
         self._released = True
         return True
 
@@ -102,7 +128,7 @@ class ColBlockQuantizedLinear(torch.nn.Module):
         if self._released:
             qw, scales, zeros = self.reference_buffers()
             self._released = False
-            self.quant_weight, self.scales, self.zeros = qw, scales, zeros
+            self._set_reference(qw, scales, zeros)
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         # the state-dict contract (<name>.quant_weight / .scales / .zeros / .bias) holds whether or not the buffers are resident
@@ -117,18 +143,16 @@ class ColBlockQuantizedLinear(torch.nn.Module):
         self.restore_reference()
         super()._load_from_state_dict(*args, **kwargs)
         self._packed = None
-        self.image_epoch += 1
+        self.image_epoch = next_epoch()
 
     def _apply(self, fn, *args, **kwargs):
         # .to(device) / .to(dtype): keep quant_weight's column-major layout and drop the derived copy
         self.restore_reference()
         self._packed = None
-        self.image_epoch += 1
-        qw = self.quant_weight
+        self.image_epoch = next_epoch()
         out = super()._apply(fn, *args, **kwargs)
         if self.quant_weight.stride() != (1, self.out_features):
-            self.quant_weight = self.quant_weight.t().contiguous().t()
-        del qw
+            self._buffers["quant_weight"] = self.quant_weight.t().contiguous().t()
         return out
 
     # -------------------------------------------------------------------------------------- HIP path

@@ -82,6 +82,7 @@ def build_synthetic_model(config: Config, mode=None, seed: int = 1234, device="c
     from .model import GPT
     from .quantize.gptq import ColBlockQuantizedLinear, pack_nibbles, rtn_quantize
     from .utils import quantization
+    from .weights import weights_changed
 
     dev = torch.device(device)
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -96,8 +97,6 @@ def build_synthetic_model(config: Config, mode=None, seed: int = 1234, device="c
             module.zeros = z
             if module.bias is not None:
                 module.bias.zero_()
-            module._packed = None
-            module.image_epoch += 1
             del w, q
         elif isinstance(module, torch.nn.Linear):
             w = torch.randn((module.out_features, module.in_features), generator=gen, device=dev) * 0.02
@@ -115,4 +114,6 @@ def build_synthetic_model(config: Config, mode=None, seed: int = 1234, device="c
             if getattr(module, "bias", None) is not None:
                 module.bias.data.zero_()
             module.eps = config.norm_eps
-    return model.to(torch.bfloat16).eval()
+    model = model.to(torch.bfloat16).eval()
+    weights_changed(model)  # (the fills above go through .data; .to() has said so already - this is the rule spelt out)
+    return model
