@@ -86,8 +86,25 @@ int parrot_w4_gemv(const void* packed, const void* packed2, const void* x, int l
  * parrot_rmsnorm / parrot_layernorm first and pass norm == NULL), and
  * `workspace` holds parrot_gemm_workspace_floats(M, N, K, group, epilogue) floats: the normalised rows of a fused norm,
  * the per-group activation sums (int4) and, for launches with too few tiles to fill the chip (short prompts), the
- * split-K partial results that a second stage sums in a fixed order.  group = 0 asks for the bf16 GEMM's needs.   */
+ * split-K partial results that a second stage sums in a fixed order.  group = 0 asks for the bf16 GEMM's needs.
+ * One plan per call (csrc/gemm_plan.h) decides the kernel, the split and this layout, regions in this order, in floats:
+ *   xn     ceil(M K / 2)          normalised rows (bf16, leading dimension K)      only when parrot_w4_gemm fuses the norm
+ *   xs     ceil(M / 128) 128 x G  per-group activation sums [group][row]           int4 on the LDS-DMA kernel (G = groups per row)
+ *          M x G                  the same as [row][group]                         int4 on the first-generation kernel
+ *   part   ksplit x M x N         fp32 partial results                             only when K is split (ksplit > 1)
+ *   part2  ksplit x M x N         those of the second weight                       only when a SWIGLU call is split
+ * bf16 and codebook calls have part / part2 only.  parrot_gemm_workspace_floats cannot see a fused norm or a codebook: it returns
+ * the largest total over those variants, never less than the plan of a call with its five arguments takes. */
 int64_t parrot_gemm_workspace_floats(int M, int N, int K, int group, int epilogue);
+/* How a prompt-GEMM entry point will run a call with M > 8: host arithmetic only, no HIP call.
+ * kind 0 bf16, 1 int4 (group as for parrot_w4_gemm), 2 codebook.  norm_kind != 0 asks whether parrot_w4_gemm would fuse that norm.
+ * out[12] = route, ksplit, norm_fused, xn_off, xn_len, xs_off, xs_len, part_off, part_len, part2_off, part2_len, total (floats).
+ * route: 0 first-generation kernel, 1 LDS-DMA bf16, 2 LDS-DMA int4, 3 LDS-DMA codebook.  norm_fused == 0 with norm_kind != 0: the
+ * entry point does not take that norm, and the plan is that of the same call on rows normalised beforehand (norm == NULL).
+ * Returns PARROT_OK, or the code the entry point itself returns for a shape or an argument it does not take (ldx, alignment,
+ * epilogue, an unknown norm kind: PARROT_EINVAL; K, group or block the kernels do not take: PARROT_EUNSUPPORTED); a norm that
+ * is known but not fused is answered by norm_fused == 0, not by an error. */
+int parrot_gemm_plan(int kind, int M, int N, int K, int group, int epilogue, int ldx, int aligned16, int norm_kind, int64_t* out);
 int parrot_w4_gemm(const void* packed, const void* packed2, const void* x, int ldx, int M,
                    const void* bias, const void* residual, int ldr, void* out, int ldo, int N,
                    int K, int group, int epilogue, const parrot_norm_t* norm, void* workspace,

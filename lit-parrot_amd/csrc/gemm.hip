@@ -17,14 +17,14 @@
 #include <stdlib.h>
 
 #include "parrot_common.h"
-#include "w4_plan.h"
+#include "gemm_plan.h"
 
 namespace parrot {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-constexpr int GBK = 32;  // K-tile; the M x N tile is a template parameter (128 x 128 for long prompts, 64 x 64 to fill the chip on short ones)
+// K-tile GBK = 32 (gemm_plan.h); the M x N tile is a template parameter (128 x 128 for long prompts, 64 x 64 to fill the chip on short ones)
 constexpr int GLD = 40;  // LDS row stride in bf16 elements (80 B)
 
 // sum of the activations of every (row, quantisation group): xsum[m][g] = sum_{k in group g} x[m][k]
@@ -68,7 +68,7 @@ gemm_kernel(const bf16_t* __restrict__ A, int lda, int M, const void* __restrict
     const int ngroups = W4 ? plan.ngroups : 1;
     constexpr int IM = GBM / 64, JN = GBN / 64;  // 32x32 MFMA tiles per wave: each wave owns (GBM/2) x (GBN/2)
     constexpr int AIT = GBM / 64;                // 16-byte A pieces per thread per K-tile
-    constexpr int BIT = W4 ? (GBN / 64) : (GBN / 64);  // bf16: 16-byte pieces; int4: one dword (8 weights) per piece
+    constexpr int BIT = GBN / 64;                // bf16: 16-byte pieces; int4: one dword (8 weights) per piece
 
     float* xs_l = reinterpret_cast<float*>(gemm_smem);
     if (W4 && xs_lds) {
@@ -325,84 +325,90 @@ int launch_splitk_epilogue(const float* part, const float* part2, int ksplit, in
                   M, N, bias, residual, ldr, out, ldo, epi);
 }
 
-// 128 x 128 tiles only when they alone give the chip >= 2 workgroups per CU; otherwise 64 x 64 (4x the workgroups)
-static bool gemm_big_tiles(int M, int N) {
-    const int env = tune_env("PARROT_GEMM_BIG_MIN", 512);  // PARROT_GEMM_BIG_MIN: minimum number of 128 x 128 tiles for the big-tile kernel (experiment hook)
-    return (int64_t)((M + 127) / 128) * ((N + 127) / 128) >= env;
-}
-
-// K splits for launches with too few tiles to fill the chip (short prompts): equal ranges of whole quantisation groups,
-// at least 8 K-tiles each, at most 8 splits, aiming at >= ~1536 workgroups
-static int gemm_ksplit(int M, int N, int K, int gs_tiles) {
-    const int env = tune_env("PARROT_GEMM_KSPLIT", -2);  // PARROT_GEMM_KSPLIT: 0 = never split (A/B), n = force
-    if (env == 0) return 1;
-    const int64_t tiles = gemm_big_tiles(M, N) ? (int64_t)((M + 127) / 128) * ((N + 127) / 128) : (int64_t)((M + 63) / 64) * ((N + 63) / 64);
-    const int ktiles = K / GBK;
-    int ks = env > 0 ? env : (int)(1536 / (tiles > 0 ? tiles : 1));
-    if (ks > 8) ks = 8;
-    while (ks > 1 && (ktiles % (ks * gs_tiles) != 0 || ktiles / ks < 8)) --ks;
-    return ks < 1 ? 1 : ks;
-}
-
-// launch the tiles (x ksplit) and, when K was split, the second stage
+// launch the tiles (x ksplit): the activation sums and the partial results live where the plan says
 template <bool W4>
 static int gemm_launch(int kid, const void* Wp, const void* W2p, const void* x, int ldx, int M, const void* bias, const void* residual,
-                       int ldr, void* out, int ldo, int N, int K, int epilogue, const float* xsum, float* part_ws, const W4Plan& plan,
-                       int gs_tiles, hipStream_t st) {
-    const int ksplit = gemm_ksplit(M, N, K, gs_tiles);
-    float* part = ksplit > 1 ? part_ws : nullptr;
-    float* part2 = (ksplit > 1 && epilogue == PARROT_EPI_SWIGLU) ? part_ws + (int64_t)ksplit * M * N : nullptr;
-    PARROT_REQUIRE(ksplit == 1 || part_ws != nullptr, "gemm: this shape splits K %d ways and needs the workspace of parrot_gemm_workspace_floats", ksplit);
-    int rc;
+                       int ldr, void* out, int ldo, int N, int K, int epilogue, float* ws, const GemmPlan& gp, const W4Plan& plan,
+                       hipStream_t st) {
+    const int ksplit = gp.ksplit;
+    PARROT_REQUIRE(ksplit == 1 || ws != nullptr, "gemm: this shape splits K %d ways and needs the workspace of parrot_gemm_workspace_floats", ksplit);
+    const float* xsum = W4 ? ws + gp.xs.off : nullptr;
+    float* part = gp.part.len ? ws + gp.part.off : nullptr;
+    float* part2 = gp.part2.len ? ws + gp.part2.off : nullptr;
 #define PARROT_GEMM_GO2(BMV, BNV, SPLITV, SWIV)                                                                                \
-    rc = launch(kid, gemm_kernel<W4, BMV, BNV, SPLITV, SWIV>, grid, dim3(256), in_lds ? xb : 0, st, (const bf16_t*)x, ldx, M, Wp, W2p, N, \
-                K, xsum, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, in_lds, plan, ksplit, part, part2)
+    return launch(kid, gemm_kernel<W4, BMV, BNV, SPLITV, SWIV>, grid, dim3(256), in_lds ? xb : 0, st, (const bf16_t*)x, ldx, M, Wp, W2p, N, \
+                  K, xsum, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, in_lds, plan, ksplit, part, part2)
 #define PARROT_GEMM_GO(BMV, BNV, SPLITV)                       \
-    if (epilogue == PARROT_EPI_SWIGLU)                         \
-        PARROT_GEMM_GO2(BMV, BNV, SPLITV, true);               \
-    else                                                       \
-        PARROT_GEMM_GO2(BMV, BNV, SPLITV, false)
-    if (gemm_big_tiles(M, N)) {
+    do {                                                       \
+        if (epilogue == PARROT_EPI_SWIGLU)                     \
+            PARROT_GEMM_GO2(BMV, BNV, SPLITV, true);           \
+        PARROT_GEMM_GO2(BMV, BNV, SPLITV, false);              \
+    } while (0)
+    if (gp.tile == 128) {
         const size_t xb = W4 ? (size_t)128 * plan.ngroups * 4 : 0;
         const int in_lds = W4 && xb <= 20 * 1024;
         const dim3 grid((N + 127) / 128, (M + 127) / 128, ksplit);
-        if (ksplit > 1)
-            PARROT_GEMM_GO(128, 128, true);
-        else
-            PARROT_GEMM_GO(128, 128, false);
-    } else {
-        const size_t xb = W4 ? (size_t)64 * plan.ngroups * 4 : 0;
-        const int in_lds = W4 && xb <= 40 * 1024;
-        const dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
-        if (ksplit > 1)
-            PARROT_GEMM_GO(64, 64, true);
-        else
-            PARROT_GEMM_GO(64, 64, false);
+        if (ksplit > 1) PARROT_GEMM_GO(128, 128, true);
+        PARROT_GEMM_GO(128, 128, false);
     }
+    const size_t xb = W4 ? (size_t)64 * plan.ngroups * 4 : 0;
+    const int in_lds = W4 && xb <= 40 * 1024;
+    const dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
+    if (ksplit > 1) PARROT_GEMM_GO(64, 64, true);
+    PARROT_GEMM_GO(64, 64, false);
 #undef PARROT_GEMM_GO
 #undef PARROT_GEMM_GO2
-    if (rc != PARROT_OK || ksplit == 1) return rc;
-    const int64_t n = (int64_t)M * N;
-    return launch_splitk_epilogue((const float*)part, (const float*)part2, ksplit, M, N, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, st);
+}
+
+// the second stage of every split-K route: nothing to do after a failed launch or a one-pass plan
+static int gemm_finish(int rc, const GemmPlan& gp, const float* ws, int M, int N, const void* bias, const void* residual, int ldr, void* out,
+                       int ldo, int epilogue, hipStream_t st) {
+    if (rc != PARROT_OK || gp.ksplit == 1) return rc;
+    return launch_splitk_epilogue(ws + gp.part.off, gp.part2.len ? ws + gp.part2.off : nullptr, gp.ksplit, M, N, (const bf16_t*)bias,
+                                  (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, st);
 }
 
 // norm + per-group sums of a prompt's rows in one launch (norm.hip)
-bool norm_xsum_takes(const NormArgs& na, int d, int G);
 int norm_xsum_launch(const NormArgs& na, const void* x, int ldx, void* xn, int ldo, int M, int Mpad, int d, int G, float* xs, hipStream_t st);
-
-// second-generation bf16 kernel (gemm2.hip)
-int gemm2_ksplit(int M, int N, int K);
-bool gemm2_enabled();
+// LDS-DMA kernels (gemm2.hip)
 int gemm2_launch(const void* W, const void* x, int ldx, int M, const void* bias, const void* residual, int ldr, void* out, int ldo,
-                 int N, int K, int epilogue, float* part, hipStream_t st, int* ksplit_out);
-bool gemm2_w4_takes(const W4Plan& plan, int K);
-int gemm2_w4_ksplit(int M, int N, int K, const W4Plan& plan);
-int64_t gemm2_w4_xs_floats(int M, const W4Plan& plan);
+                 int N, int K, int epilogue, float* ws, const GemmPlan& gp, hipStream_t st);
 int gemm2_w4_launch(const void* Wq, const void* Wq2, const void* x, int ldx, int M, const void* bias, const void* residual, int ldr,
-                    void* out, int ldo, int N, int K, int epilogue, float* workspace, const W4Plan& plan, hipStream_t st, int* ksplit_out,
-                    float** part_out, float** part2_out, const void* code, bool have_xs);
-static bool gemm2_takes(int K, int ldx, int epilogue, const void* W, const void* x) {
-    return gemm2_enabled() && epilogue != PARROT_EPI_SWIGLU && K % 64 == 0 && ldx % 8 == 0 && aligned16(W) && aligned16(x);
+                    void* out, int ldo, int N, int K, int epilogue, float* ws, const GemmPlan& gp, const W4Plan& plan, hipStream_t st,
+                    const void* code);
+
+// int4 / codebook: the weight layout, then the plan; launches the LDS-DMA kernel or (int4 only) the first-generation one
+static int w4_gemm_run(int kind, const void* packed, const void* packed2, const void* code, const void* x, int ldx, int M, const void* bias,
+                       const void* residual, int ldr, void* out, int ldo, int N, int K, int group, int epilogue, const parrot_norm_t* norm,
+                       float* ws, hipStream_t st) {
+    W4Plan plan;
+    int rc = w4_make_plan(N, K, group, &plan);
+    if (rc != PARROT_OK) return rc;
+    NormArgs na;
+    rc = make_norm_args(norm, K, &na);
+    if (rc != PARROT_OK) return rc;
+    GemmPlan gp;
+    rc = gemm_make_plan(kind, M, N, K, &plan, epilogue, na.kind, &gp);
+    if (rc != PARROT_OK) return rc;
+    PARROT_UNSUPPORTED(na.kind == 0 || gp.norm_fused, "w4_gemm: the fused norm takes int4 groups of 64 / 128 on the LDS-DMA kernel; apply the norm to "
+                       "the rows first (parrot_rmsnorm / parrot_layernorm) for K=%d group=%d", K, group);
+    if (gp.norm_fused) {
+        // the norm of the prompt's rows AND the per-group sums of its output in ONE launch in front of the GEMM (instead of
+        // parrot_rmsnorm + the activation-sum pre-pass)
+        bf16_t* xn = reinterpret_cast<bf16_t*>(ws + gp.xn.off);
+        rc = norm_xsum_launch(na, x, ldx, xn, K, M, (M + G2M - 1) / G2M * G2M, K, plan.Gs * 32, ws + gp.xs.off, st);
+        if (rc != PARROT_OK) return rc;
+        x = xn, ldx = K;
+    }
+    if (gp.route != GEMM_ROUTE_GEN1) {
+        rc = gemm2_w4_launch(packed, packed2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, ws, gp, plan, st, code);
+    } else {
+        rc = launch(K_GEMM_XSUM, gemm_xsum_kernel, dim3((unsigned)((gp.xs.len + 255) / 256)), dim3(256), 0, st, (const bf16_t*)x, ldx, M, K,
+                    plan.Gs * 32, plan.ngroups, ws + gp.xs.off);
+        if (rc == PARROT_OK)
+            rc = gemm_launch<true>(K_W4_GEMM, packed, packed2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, ws, gp, plan, st);
+    }
+    return gemm_finish(rc, gp, ws, M, N, bias, residual, ldr, out, ldo, epilogue, st);
 }
 
 }  // namespace parrot
@@ -411,33 +417,36 @@ using namespace parrot;
 
 extern "C" {
 
-// floats of workspace a GEMM call needs: the per-group activation sums (int4: group != 0) + the split-K partial results
+// floats of workspace a prompt GEMM call needs: the largest plan over what the five arguments leave open (a norm in front, int4 or
+// codebook weights); layout table: include/parrot_hip.h and gemm_plan.h.  Only plans that exist are built (no error is recorded).
 int64_t parrot_gemm_workspace_floats(int M, int N, int K, int group, int epilogue) {
+    GemmPlan gp;
+    if (group == 0) return K % GBK == 0 && gemm_make_plan(GEMM_BF16, M, N, K, nullptr, epilogue, 0, &gp) == PARROT_OK ? gp.total : 0;
+    W4Plan plan;
+    if (w4_make_plan(N, K, group, &plan) != PARROT_OK) return 0;
     int64_t n = 0;
-    int gs_tiles = 1;  // bf16: any K-tile boundary will do
-    if (group != 0) {
-        if (group < 0 || group > K) group = K;
-        n += (int64_t)M * ((K + group - 1) / group);
-        gs_tiles = group / GBK > 0 ? group / GBK : 1;
-    }
-    if (K % GBK == 0) {
-        int ks = gemm_ksplit(M, N, K, gs_tiles);
-        if (group == 0 && K % 64 == 0 && epilogue != PARROT_EPI_SWIGLU && gemm2_enabled()) {  // whichever bf16 kernel ends up running
-            const int ks2 = gemm2_ksplit(M, N, K);
-            if (ks2 > ks) ks = ks2;
-        }
-        if (ks > 1) n += (int64_t)ks * M * N * (epilogue == PARROT_EPI_SWIGLU ? 2 : 1);
-    }
-    if (group != 0 && K % 32 == 0) {  // the second-generation int4 kernel lays the workspace out differently: cover both
-        W4Plan plan;
-        if (w4_make_plan(N, K, group, &plan) == PARROT_OK && gemm2_w4_takes(plan, K)) {
-            const int ks2 = gemm2_w4_ksplit(M, N, K, plan);
-            int64_t n2 = gemm2_w4_xs_floats(M, plan) + (ks2 > 1 ? (int64_t)ks2 * M * N * (epilogue == PARROT_EPI_SWIGLU ? 2 : 1) : 0);
-            if (plan.Gs == 2 || plan.Gs == 4) n2 += ((int64_t)M * K + 1) / 2;  // room for the normalised rows of a fused norm (parrot_w4_gemm)
-            if (n2 > n) n = n2;
-        }
-    }
+    for (int norm_kind = 0; norm_kind < 2; ++norm_kind)
+        if (gemm_make_plan(GEMM_W4, M, N, K, &plan, epilogue, norm_kind, &gp) == PARROT_OK && gp.total > n) n = gp.total;
+    if (gemm2_w4_takes(plan, K) && gemm_make_plan(GEMM_W4C, M, N, K, &plan, epilogue, 0, &gp) == PARROT_OK && gp.total > n) n = gp.total;
     return n;
+}
+
+int parrot_gemm_plan(int kind, int M, int N, int K, int group, int epilogue, int ldx, int aligned16, int norm_kind, int64_t* out) {
+    PARROT_REQUIRE(out != nullptr && kind >= GEMM_BF16 && kind <= GEMM_W4C, "gemm_plan: kind must be 0 (bf16), 1 (int4) or 2 (codebook)");
+    PARROT_REQUIRE(M > kMaxDecodeRows && N >= 1 && K >= 1, "gemm_plan: bad shape M=%d N=%d K=%d (M <= 8 goes to the GEMV)", M, N, K);
+    PARROT_REQUIRE(epilogue >= PARROT_EPI_NONE && epilogue <= PARROT_EPI_SWIGLU, "gemm_plan: unknown epilogue %d", epilogue);
+    PARROT_REQUIRE(ldx >= K && ldx % 8 == 0 && aligned16, "gemm_plan: W and x must be 16-byte aligned, ldx a multiple of 8 and >= K");
+    PARROT_REQUIRE(norm_kind >= 0 && norm_kind <= 2, "gemm_plan: norm_kind must be 0, 1 (RMSNorm) or 2 (LayerNorm)");
+    W4Plan plan;
+    int rc = kind == GEMM_BF16 ? PARROT_OK : w4_make_plan(N, K, group, &plan);
+    if (rc != PARROT_OK) return rc;
+    GemmPlan gp;
+    rc = gemm_make_plan(kind, M, N, K, &plan, epilogue, norm_kind, &gp);
+    if (rc != PARROT_OK) return rc;
+    const int64_t v[12] = {gp.route, gp.ksplit, gp.norm_fused, gp.xn.off, gp.xn.len, gp.xs.off, gp.xs.len, gp.part.off, gp.part.len,
+                           gp.part2.off, gp.part2.len, gp.total};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PARROT_OK;
 }
 
 int parrot_bf16_gemm(const void* W, const void* W2, const void* x, int ldx, int M, const void* bias, const void* residual,
@@ -447,19 +456,18 @@ int parrot_bf16_gemm(const void* W, const void* W2, const void* x, int ldx, int 
     int rc = check_linear_args("bf16_gemm", W, W2, x, ldx, M, residual, ldr, out, ldo, N, K, epilogue);
     if (rc != PARROT_OK) return rc;
     PARROT_UNSUPPORTED(norm == nullptr || norm->kind == 0, "bf16_gemm: apply the norm to the rows first (parrot_rmsnorm / parrot_layernorm)");
-    PARROT_UNSUPPORTED(K % GBK == 0, "bf16_gemm: K=%d must be a multiple of %d", K, GBK);
     PARROT_UNSUPPORTED(!(epilogue == PARROT_EPI_SWIGLU && bias), "bf16_gemm: SWIGLU epilogue takes no bias");
     PARROT_REQUIRE(M <= 65535 * 64, "bf16_gemm: M too large");
-    if (gemm2_takes(K, ldx, epilogue, W, x)) {
-        int ks = 1;
-        rc = gemm2_launch(W, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, (float*)workspace, (hipStream_t)stream, &ks);
-        if (rc != PARROT_OK || ks == 1) return rc;
-        const int64_t n = (int64_t)M * N;
-        return launch_splitk_epilogue((const float*)workspace, (const float*)nullptr, ks, M, N, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, (hipStream_t)stream);
-    }
-    W4Plan plan = {};
-    return gemm_launch<false>(K_BF16_GEMM, W, W2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, nullptr, (float*)workspace,
-                              plan, 1, (hipStream_t)stream);
+    GemmPlan gp;
+    rc = gemm_make_plan(GEMM_BF16, M, N, K, nullptr, epilogue, 0, &gp);
+    if (rc != PARROT_OK) return rc;
+    float* ws = (float*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    if (gp.route == GEMM_ROUTE_G2)
+        rc = gemm2_launch(W, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, ws, gp, st);
+    else
+        rc = gemm_launch<false>(K_BF16_GEMM, W, W2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, ws, gp, W4Plan{}, st);
+    return gemm_finish(rc, gp, ws, M, N, bias, residual, ldr, out, ldo, epilogue, st);
 }
 
 int parrot_w4_gemm(const void* packed, const void* packed2, const void* x, int ldx, int M, const void* bias,
@@ -467,48 +475,12 @@ int parrot_w4_gemm(const void* packed, const void* packed2, const void* x, int l
                    const parrot_norm_t* norm, void* workspace, void* stream) {
     if (M <= 8)
         return parrot_w4_gemv(packed, packed2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, group, epilogue, norm, stream);
-    int rc = check_linear_args("w4_gemm", packed, packed2, x, ldx, M, residual, ldr, out, ldo, N, K, epilogue);
+    const int rc = check_linear_args("w4_gemm", packed, packed2, x, ldx, M, residual, ldr, out, ldo, N, K, epilogue);
     if (rc != PARROT_OK) return rc;
     PARROT_REQUIRE(workspace != nullptr, "w4_gemm: workspace of parrot_gemm_workspace_floats(M, N, K, group, epilogue) floats required");
     PARROT_UNSUPPORTED(!(epilogue == PARROT_EPI_SWIGLU && bias), "w4_gemm: SWIGLU epilogue takes no bias");
-    W4Plan plan;
-    rc = w4_make_plan(N, K, group, &plan);
-    if (rc != PARROT_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    NormArgs na;
-    rc = make_norm_args(norm, K, &na);
-    if (rc != PARROT_OK) return rc;
-    const bool fused_norm = na.kind != 0;
-    if (fused_norm) {
-        // the norm of the prompt's rows AND the per-group sums of its output in ONE launch in front of the GEMM (instead of
-        // parrot_rmsnorm + the activation-sum pre-pass): the normalised rows go to the head of the workspace
-        PARROT_UNSUPPORTED(gemm2_w4_takes(plan, K) && ldx % 8 == 0 && norm_xsum_takes(na, K, plan.Gs * 32),
-                           "w4_gemm: the fused norm takes groups of 64 / 128 on the LDS-DMA kernel; apply the norm to the rows first "
-                           "(parrot_rmsnorm / parrot_layernorm) for K=%d group=%d", K, group);
-        const int Mpad = (M + 127) / 128 * 128;
-        bf16_t* xn = reinterpret_cast<bf16_t*>(workspace);
-        float* ws2 = reinterpret_cast<float*>(workspace) + ((int64_t)M * K + 1) / 2;
-        rc = norm_xsum_launch(na, x, ldx, xn, K, M, Mpad, K, plan.Gs * 32, ws2, st);
-        if (rc != PARROT_OK) return rc;
-        x = xn, ldx = K, workspace = ws2;
-    }
-    if (gemm2_w4_takes(plan, K) && ldx % 8 == 0) {
-        int ks = 1;
-        float *part = nullptr, *part2 = nullptr;
-        rc = gemm2_w4_launch(packed, packed2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, (float*)workspace, plan, st, &ks,
-                             &part, &part2, nullptr, fused_norm);
-        if (rc != PARROT_OK || ks == 1) return rc;
-        const int64_t mn = (int64_t)M * N;
-        return launch_splitk_epilogue((const float*)part, (const float*)part2, ks, M, N, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, st);
-    }
-    const int G = plan.Gs * 32;
-    const int64_t n = (int64_t)M * plan.ngroups;
-    rc = launch(K_GEMM_XSUM, gemm_xsum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const bf16_t*)x, ldx, M, K, G,
-                plan.ngroups, (float*)workspace);
-    if (rc != PARROT_OK) return rc;
-    // the split-K partials follow the activation sums in the workspace
-    return gemm_launch<true>(K_W4_GEMM, packed, packed2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, (const float*)workspace,
-                             (float*)workspace + n, plan, plan.Gs, st);
+    return w4_gemm_run(GEMM_W4, packed, packed2, nullptr, x, ldx, M, bias, residual, ldr, out, ldo, N, K, group, epilogue, norm,
+                       (float*)workspace, (hipStream_t)stream);
 }
 
 // NF4 / FP4 (bitsandbytes 4-bit) prompt rows on the matrix cores: the codebook variant of the int4 LDS-DMA kernel.  Needs
@@ -518,24 +490,14 @@ int parrot_w4c_gemm(const void* packed, const void* packed2, const void* code16_
                     const parrot_norm_t* norm, void* workspace, void* stream) {
     if (M <= 8)
         return parrot_w4c_gemv(packed, packed2, code16_bf16, x, ldx, M, bias, residual, ldr, out, ldo, N, K, block, epilogue, norm, stream);
-    int rc = check_linear_args("w4c_gemm", packed, packed2, x, ldx, M, residual, ldr, out, ldo, N, K, epilogue);
+    const int rc = check_linear_args("w4c_gemm", packed, packed2, x, ldx, M, residual, ldr, out, ldo, N, K, epilogue);
     if (rc != PARROT_OK) return rc;
     PARROT_REQUIRE(code16_bf16 != nullptr, "w4c_gemm: codebook pointer is null");
     PARROT_UNSUPPORTED(norm == nullptr || norm->kind == 0, "w4c_gemm: apply the norm to the rows first (parrot_rmsnorm / parrot_layernorm)");
     PARROT_REQUIRE(workspace != nullptr, "w4c_gemm: workspace of parrot_gemm_workspace_floats(M, N, K, block, epilogue) floats required");
     PARROT_UNSUPPORTED(!(epilogue == PARROT_EPI_SWIGLU && bias), "w4c_gemm: SWIGLU epilogue takes no bias");
-    W4Plan plan;
-    rc = w4_make_plan(N, K, block, &plan);
-    if (rc != PARROT_OK) return rc;
-    PARROT_UNSUPPORTED(gemm2_w4_takes(plan, K) && ldx % 8 == 0, "w4c_gemm: needs K %% 64 == 0, blocks that are multiples of 64 and 16-byte rows (K=%d block=%d)", K, block);
-    hipStream_t st = (hipStream_t)stream;
-    int ks = 1;
-    float *part = nullptr, *part2 = nullptr;
-    rc = gemm2_w4_launch(packed, packed2, x, ldx, M, bias, residual, ldr, out, ldo, N, K, epilogue, (float*)workspace, plan, st, &ks, &part,
-                         &part2, code16_bf16, false);
-    if (rc != PARROT_OK || ks == 1) return rc;
-    const int64_t mn = (int64_t)M * N;
-    return launch_splitk_epilogue((const float*)part, (const float*)part2, ks, M, N, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo, epilogue, st);
+    return w4_gemm_run(GEMM_W4C, packed, packed2, code16_bf16, x, ldx, M, bias, residual, ldr, out, ldo, N, K, block, epilogue, nullptr,
+                       (float*)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -20,14 +20,14 @@
 #include <type_traits>
 
 #include "parrot_common.h"
-#include "w4_plan.h"
+#include "gemm_plan.h"
 
 namespace parrot {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-constexpr int G2M = 128, G2N = 128, G2K = 64;
+// (tile constants G2M, G2N, G2K: gemm_plan.h)
 #ifndef PARROT_G2_PRIO
 #define PARROT_G2_PRIO 0
 #endif
@@ -207,32 +207,6 @@ gemm2_kernel(const bf16_t* __restrict__ A, int lda, int M, const bf16_t* __restr
         }
 }
 
-// tile rows: 256 (8 waves, one workgroup per CU) for prompts that fill whole 256-row tiles as well as 128-row ones
-int gemm2_wm(int M) {
-    const int env = tune_env("PARROT_GEMM2_WM", 0);  // PARROT_GEMM2_WM = 2 | 4 (A/B)
-    if (env == 2 || env == 4) return env;
-    return (M + 255) / 256 * 256 == (M + 127) / 128 * 128 ? 4 : 2;
-}
-
-// K splits when the tiles alone leave most of the chip idle: aim at ~512 workgroups of 128 x 128 (two fit a CU) or 256 of
-// 256 x 128 (one per CU), whole 64-deep steps, at least 8 per split
-int gemm2_ksplit(int M, int N, int K) {
-    const int wm = gemm2_wm(M), tm = wm * 64;
-    const int64_t tiles = (int64_t)((M + tm - 1) / tm) * ((N + G2N - 1) / G2N);
-    const int ktiles = K / G2K;
-    const int target = tune_env("PARROT_GEMM2_SPLIT_TARGET", wm == 4 ? 256 : 512);  // PARROT_GEMM2_SPLIT_TARGET: workgroups to aim at when splitting
-    const int full = wm == 4 ? 128 : 256;  // more tiles than this: no split
-    int ks = tiles > full ? 1 : (int)(target / (tiles > 0 ? tiles : 1));
-    if (ks > 8) ks = 8;
-    while (ks > 1 && ktiles / ks < 8) --ks;  // (uneven ranges are fine: split z owns steps [z kt / ks, (z + 1) kt / ks))
-    return ks < 1 ? 1 : ks;
-}
-
-bool gemm2_enabled() {
-    const int env = tune_env("PARROT_GEMM2", 1);  // PARROT_GEMM2=0: A/B against the first-generation kernel
-    return env != 0;
-}
-
 static int g2_largest_divisor_le(int n, int cap) {
     for (int d = cap < n ? cap : n; d > 1; --d)
         if (n % d == 0) return d;
@@ -240,12 +214,12 @@ static int g2_largest_divisor_le(int n, int cap) {
 }
 
 int gemm2_launch(const void* W, const void* x, int ldx, int M, const void* bias, const void* residual, int ldr, void* out, int ldo,
-                 int N, int K, int epilogue, float* part, hipStream_t st, int* ksplit_out) {
+                 int N, int K, int epilogue, float* ws, const GemmPlan& gp, hipStream_t st) {
     const int nbuf_env = tune_env("PARROT_GEMM2_NBUF", 0);  // PARROT_GEMM2_NBUF = 2 | 3 (A/B)
-    const int ks = gemm2_ksplit(M, N, K);
-    *ksplit_out = ks;
-    PARROT_REQUIRE(ks == 1 || part != nullptr, "bf16_gemm: this shape splits K %d ways and needs the workspace of parrot_gemm_workspace_floats", ks);
-    const int wm = gemm2_wm(M), tm = wm * 64;
+    const int ks = gp.ksplit;
+    PARROT_REQUIRE(ks == 1 || ws != nullptr, "bf16_gemm: this shape splits K %d ways and needs the workspace of parrot_gemm_workspace_floats", ks);
+    float* part = ws + gp.part.off;
+    const int tm = gp.tile, wm = tm / 64;
     G2Map mp;
     mp.MT = (M + tm - 1) / tm;
     mp.NT = (N + G2N - 1) / G2N;
@@ -729,58 +703,20 @@ gemm2_w4_kernel(const bf16_t* __restrict__ A, int lda, int M, const uint4* __res
         }
 }
 
-// the int4 kernel takes whole K-steps per group and slab boundaries on K-step boundaries
-bool gemm2_w4_takes(const W4Plan& plan, int K) {
-    if (!gemm2_enabled() || K % G2K != 0 || plan.Gs % 2 != 0) return false;
-    for (int c = 0; c < plan.nslabs; ++c)
-        if (plan.slab[c].slice0 % 2 != 0) return false;
-    return true;
-}
-
-// tile shape of the int4 kernel (wave columns)
-int gemm2_w4_wn(int M) {
-    const int env = tune_env("PARROT_GEMM2_W4_WN", 0);  // PARROT_GEMM2_W4_WN = 2 | 4 (A/B)
-    (void)M;
-    // measured (Llama-2-7B int4, 128- and 32-token prompts, uneven split-K): WN = 2 3.97 / 3.80 ms, WN = 4 4.77 / 4.33 ms - the wide
-    // shape does not pay; it stays selectable for A/B
-    return env == 4 ? 4 : 2;
-}
-
-int gemm2_w4_ksplit(int M, int N, int K, const W4Plan& plan) {
-    const int wn = gemm2_w4_wn(M);
-    const int tn = wn * 64;
-    const int64_t tiles = (int64_t)((M + G2M - 1) / G2M) * ((N + tn - 1) / tn);
-    const int ktiles = K / G2K, Gt = plan.Gs / 2;
-    const int env_target = tune_env("PARROT_GEMM2_W4_SPLIT_TARGET", 0), env_max = tune_env("PARROT_GEMM2_W4_KSMAX", 8);  // (A/B)
-    const int target = env_target > 0 ? env_target : (wn == 4 ? 256 : 512);  // workgroups that fill the chip
-    // launches with fewer tiles than this split K; 256 tiles still split two ways: two workgroups fit a CU (Falcon-40B 128-token prefill 25.8 -> 23.2 ms)
-    const int thr = tune_env("PARROT_GEMM2_W4_SPLIT_BELOW", 257);
-    int ks = tiles >= (wn == 4 ? 128 : thr) ? 1 : (int)(target / (tiles > 0 ? tiles : 1));
-    if (ks > env_max) ks = env_max;
-    const int G_all = (ktiles + Gt - 1) / Gt;
-    while (ks > 1 && (G_all / ks < 1 || ktiles / ks < 4)) --ks;  // whole groups per split, ranges need not be equal
-    return ks < 1 ? 1 : ks;
-}
-
-int64_t gemm2_w4_xs_floats(int M, const W4Plan& plan) { return (int64_t)((M + G2M - 1) / G2M) * G2M * plan.ngroups; }
-
 int gemm2_w4_launch(const void* Wq, const void* Wq2, const void* x, int ldx, int M, const void* bias, const void* residual, int ldr,
-                    void* out, int ldo, int N, int K, int epilogue, float* workspace, const W4Plan& plan, hipStream_t st, int* ksplit_out,
-                    float** part_out, float** part2_out, const void* code, bool have_xs) {
+                    void* out, int ldo, int N, int K, int epilogue, float* ws, const GemmPlan& gp, const W4Plan& plan, hipStream_t st,
+                    const void* code) {
     const int Mpad = (M + G2M - 1) / G2M * G2M;
-    const int64_t nxs = code ? 0 : (int64_t)Mpad * plan.ngroups;  // codebook weights need no activation sums
+    float* xs = ws + gp.xs.off;
     int rc = PARROT_OK;
-    if (!code && !have_xs)  // (have_xs: the caller's fused norm wrote the sums at the head of the workspace)
-        rc = launch(K_GEMM_XSUM, gemm2_xsum_kernel, dim3((unsigned)((nxs * 16 + 255) / 256)), dim3(256), 0, st, (const bf16_t*)x, ldx, M, Mpad, K,
-                    plan.Gs * 32, plan.ngroups, workspace);
+    if (!code && !gp.norm_fused)  // (codebook weights need no activation sums; a fused norm has written them already)
+        rc = launch(K_GEMM_XSUM, gemm2_xsum_kernel, dim3((unsigned)((gp.xs.len * 16 + 255) / 256)), dim3(256), 0, st, (const bf16_t*)x, ldx, M, Mpad,
+                    K, plan.Gs * 32, plan.ngroups, xs);
     if (rc != PARROT_OK) return rc;
-    const int ks = gemm2_w4_ksplit(M, N, K, plan);
-    *ksplit_out = ks;
-    float* part = workspace + nxs;
-    float* part2 = part + (int64_t)ks * M * N;
-    *part_out = part;
-    *part2_out = epilogue == PARROT_EPI_SWIGLU ? part2 : nullptr;
-    const int wn = gemm2_w4_wn(M);
+    const int ks = gp.ksplit;
+    float* part = ws + gp.part.off;
+    float* part2 = ws + gp.part2.off;
+    const int wn = gp.tile / 64;
     G2Map mp;
     mp.MT = (M + G2M - 1) / G2M;
     mp.NT = (N + wn * 64 - 1) / (wn * 64);
@@ -794,7 +730,7 @@ int gemm2_w4_launch(const void* Wq, const void* Wq2, const void* x, int ldx, int
     const dim3 grid((unsigned)total);
 #define PARROT_G2W_GO_CB(SPLITV, SWIV, WNV, CBV)                                                                                    \
     return launch(CBV ? K_W4C_GEMM : K_W4_GEMM, gemm2_w4_kernel<SPLITV, SWIV, WNV, CBV>, grid, dim3(WNV * 128), 0, st, (const bf16_t*)x, ldx, \
-                  M, (const uint4*)Wq, (const uint4*)Wq2, N, K, (const float*)workspace, Mpad, (const bf16_t*)bias, (const bf16_t*)residual, \
+                  M, (const uint4*)Wq, (const uint4*)Wq2, N, K, (const float*)xs, Mpad, (const bf16_t*)bias, (const bf16_t*)residual, \
                   ldr, (bf16_t*)out, ldo, epilogue, plan, ks, part, part2, mp, (const uint32_t*)code)
 #define PARROT_G2W_GO(SPLITV, SWIV, WNV) PARROT_G2W_GO_CB(SPLITV, SWIV, WNV, false)
     if (code) {  // codebook weights: the 128 x 128 shape only

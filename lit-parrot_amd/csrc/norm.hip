@@ -7,6 +7,7 @@
 // upcast): sq = bf16(x*x); ms = bf16(mean_fp32(sq)); r = bf16(rsqrt(bf16(ms + eps)));
 // out = bf16(w * bf16(x * r)).  LayerNorm is torch's: fp32 statistics, one rounding at the output.
 #include "parrot_common.h"
+#include "gemm_plan.h"
 
 namespace parrot {
 
@@ -135,7 +136,7 @@ static int norm_check(const char* who, const void* x, int ldx, const void* w, co
 }
 
 // the norm of a prompt's rows + their per-group sums in one launch (parrot_w4_gemm with a norm argument)
-bool norm_xsum_takes(const NormArgs& na, int d, int G) { return (na.kind == 1 || na.kind == 2) && (G == 64 || G == 128) && d % G == 0 && d <= kNormThreads * 8 * kNormV; }
+static_assert(kNormXsumMaxD == kNormThreads * 8 * kNormV, "norm_xsum_takes (gemm_plan.h) promises rows this kernel cannot hold");
 int norm_xsum_launch(const NormArgs& na, const void* x, int ldx, void* xn, int ldo, int M, int Mpad, int d, int G, float* xs, hipStream_t st) {
     const int rc = norm_check("w4_gemm (norm)", x, ldx, na.weight, xn, ldo, M, d);
     if (rc != PARROT_OK) return rc;

@@ -6,42 +6,11 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "../../include/parrot_hip.h"
+#include "parrot_host.h"
 
 namespace parrot {
 
-// ---------------------------------------------------------------- errors
-void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
-
-#define PARROT_REQUIRE(cond, ...)                 \
-    do {                                          \
-        if (!(cond)) {                            \
-            ::parrot::set_error(__VA_ARGS__);     \
-            return PARROT_EINVAL;                 \
-        }                                         \
-    } while (0)
-
-#define PARROT_UNSUPPORTED(cond, ...)             \
-    do {                                          \
-        if (!(cond)) {                            \
-            ::parrot::set_error(__VA_ARGS__);     \
-            return PARROT_EUNSUPPORTED;           \
-        }                                         \
-    } while (0)
-
-// The A/B switches behind the measurements of DESIGN.md exist only in a diagnostic build (hipcc -DPARROT_DIAG, `python
-// lit-parrot_amd/_build.py --diag`): the shipped library reads no environment variable and keeps no tuning state.
-#ifdef PARROT_DIAG
-inline int tune_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-#else
-inline int tune_env(const char*, int dflt) { return dflt; }
-#endif
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // argument checks shared by every Linear-shaped entry point
 inline int check_linear_args(const char* who, const void* W, const void* W2, const void* x, int ldx, int M,

@@ -1,6 +1,10 @@
 // W4K layout plan (shared by w4.hip and persist.hip): how the K axis of an int4 matrix is cut into per-wave slabs.
+// The layout (structs and w4_make_plan) is host arithmetic and also compiles without HIP (gemm_plan.h); the dot products need hipcc.
 #pragma once
+#include "parrot_host.h"
+#ifdef __HIPCC__
 #include "parrot_common.h"
+#endif
 
 namespace parrot {
 
@@ -62,6 +66,7 @@ inline int w4_make_plan(int N, int K, int group, W4Plan* p) {
     return PARROT_OK;
 }
 
+#ifdef __HIPCC__
 // fp32 sum over one 16-byte slice (32 weights) of x[k] * (128 + q[k]); xr = the lane's 16 packed bf16 activation pairs
 // (a & mask) | magic in ONE instruction.  The compiler emits v_and_b32 + v_or_b32 with two literals here (gfx9 VOP3
 // takes no literal and one scalar operand): with the magic held in a VGPR and the mask in an SGPR the fused form is legal,
@@ -146,5 +151,6 @@ __device__ __forceinline__ float w4c_pairs_dot(const uint32_t (&pairs)[16], cons
     }
     return p0 + p1;
 }
+#endif  // __HIPCC__
 
 }  // namespace parrot

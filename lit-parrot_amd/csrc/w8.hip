@@ -12,6 +12,7 @@
 
 #include <stdlib.h>
 
+#include "gemm_plan.h"
 #include "gemv_common.h"
 
 namespace parrot {
@@ -882,16 +883,6 @@ w8_sub_gemm_kernel(const __half* __restrict__ subA, const __half* __restrict__ s
     }
 }
 
-static int w8_gemm2_ksplit(int M, int N, int K) {
-    const int64_t tiles = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-    const int ktiles = K / 128;
-    const int target = tune_env("PARROT_W8_SPLIT_TARGET", 512);  // PARROT_W8_SPLIT_TARGET: workgroups to aim at when splitting K
-    int ks = tiles > 256 ? 1 : (int)(target / (tiles > 0 ? tiles : 1));  // up to 256 tiles: split, two workgroups fit a CU
-    if (ks > 8) ks = 8;
-    while (ks > 1 && ktiles / ks < 4) --ks;
-    return ks < 1 ? 1 : ks;
-}
-
 }  // namespace parrot
 
 using namespace parrot;
@@ -1003,12 +994,10 @@ int parrot_w8_gemv_fused(const void* CB, const void* SCB, const void* x, float t
 }
 
 
-/* LLM.int8 prompt rows on the LDS-DMA structure: bytes of workspace parrot_w8_gemm needs (int32 sums per K range, x2 for SWIGLU) */
+/* LLM.int8 prompt rows on the LDS-DMA structure: bytes of workspace parrot_w8_gemm needs (the layout is W8GemmPlan's, gemm_plan.h) */
 int64_t parrot_w8_gemm_workspace_bytes(int M, int N, int K, int epilogue) {
     if (M <= 8 || K % 128 != 0) return 0;
-    const int64_t nw = epilogue == PARROT_EPI_SWIGLU ? 2 : 1;
-    // int32 sums + fp32 outlier part, then the fp16 operands of the outlier GEMM: A[:, idx] (M x K at worst) and dequant(CB[:, idx])
-    return ((int64_t)w8_gemm2_ksplit(M, N, K) + 1) * M * N * 4 * nw + ((int64_t)M + nw * N) * K * 2 + 64;
+    return w8_gemm_make_plan(M, N, K, epilogue).total;
 }
 
 int parrot_w8_gemm(const void* CB, const void* SCB, const void* xq, const void* xout, const void* sca, const void* nout, const void* oidx,
@@ -1026,9 +1015,11 @@ int parrot_w8_gemm(const void* CB, const void* SCB, const void* xq, const void* 
     const bool swi = epilogue == PARROT_EPI_SWIGLU;
     const int8_t* CB2 = swi ? (const int8_t*)CB + (int64_t)N * K : nullptr;
     const float* SCB2 = swi ? (const float*)SCB + N : nullptr;
-    const int ks = w8_gemm2_ksplit(M, N, K);
-    int32_t* part = (int32_t*)workspace;
-    int32_t* part2 = swi ? part + (int64_t)ks * M * N : nullptr;
+    const W8GemmPlan wp = w8_gemm_make_plan(M, N, K, epilogue);
+    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
+    const int ks = wp.ks;
+    int32_t* part = (int32_t*)(ws + wp.part);
+    int32_t* part2 = swi ? (int32_t*)(ws + wp.part2) : nullptr;
     const dim3 grid((N + 127) / 128, (M + 127) / 128, ks);
     int rc = launch(K_W8_GEMM, w8_gemm2_kernel, grid, dim3(256), 0, st, (const int8_t*)xq, (const int8_t*)CB, M, N, K, ks, part);
     if (rc != PARROT_OK) return rc;
@@ -1037,11 +1028,11 @@ int parrot_w8_gemm(const void* CB, const void* SCB, const void* xq, const void* 
         if (rc != PARROT_OK) return rc;
     }
     PARROT_REQUIRE(M <= 65535, "w8_gemm: M too large");
-    float* O1 = (float*)(part + (int64_t)ks * M * N * (swi ? 2 : 1));
-    float* O2 = swi ? O1 + (int64_t)M * N : nullptr;
+    float* O1 = (float*)(ws + wp.O1);
+    float* O2 = swi ? (float*)(ws + wp.O2) : nullptr;
     // the mixed-precision part: gather the call's outlier columns once, one fp16 GEMM per weight
-    __half* subA = reinterpret_cast<__half*>((reinterpret_cast<uintptr_t>(O1 + (int64_t)M * N * (swi ? 2 : 1)) + 15) & ~(uintptr_t)15);
-    __half* subB = subA + (int64_t)M * K;
+    __half* subA = (__half*)(ws + wp.subA);
+    __half* subB = (__half*)(ws + wp.subB);
     const int Ntot = swi ? 2 * N : N;
     rc = launch(K_W8_OUTLIER, w8_sub_gather_kernel, dim3((unsigned)(M + Ntot < 2048 ? M + Ntot : 2048)), dim3(256), 0, st, (const float*)xout,
                 (const int8_t*)CB, (const float*)SCB, (const int32_t*)nout, (const int32_t*)oidx, subA, subB, M, Ntot, K);

@@ -172,16 +172,19 @@ W4_GEMM_FUSED_NORM = True  # (False: the stand-alone norm kernels in front of th
 def w4_linear(packed: torch.Tensor, N: int, K: int, group: int, x: torch.Tensor, out: torch.Tensor, *, bias=None,
               epilogue=EPI_NONE, residual=None, packed2=None, norm: Optional[Norm] = None) -> torch.Tensor:
     _rows(x, "w4_linear"), _rows(out, "w4_linear")
-    # prompts on groups of 64 / 128: parrot_w4_gemm applies the norm itself - one launch writes the normalised rows AND the per-group
-    # sums the int4 kernel folds its zero points with (instead of parrot_rmsnorm + the activation-sum pre-pass)
-    fused = (norm is not None and W4_GEMM_FUSED_NORM and x.shape[0] > GEMV_MAX_ROWS and group in (64, 128) and K % group == 0
-             and K <= 16384 and x.stride(0) % 8 == 0)
-    if not fused:
-        x, norm = _prenorm(x, norm)
     M = x.shape[0]
     if x.shape[1] != K or out.shape[1] != N:
         raise ParrotHipError(f"w4_linear: x {tuple(x.shape)} / out {tuple(out.shape)} do not match N={N} K={K}")
     lib = _hip.load()
+    # prompts: where parrot_w4_gemm says it applies the norm itself, one launch writes the normalised rows AND the per-group sums the
+    # int4 kernel folds its zero points with (instead of parrot_rmsnorm + the activation-sum pre-pass)
+    fused = False
+    if norm is not None and W4_GEMM_FUSED_NORM and M > GEMV_MAX_ROWS:
+        plan = (C.c_int64 * 12)()
+        rc = lib.parrot_gemm_plan(1, M, N, K, group, epilogue, x.stride(0), int(ptr(x) % 16 == 0 and ptr(packed) % 16 == 0), norm.kind, plan)
+        fused = rc == 0 and plan[2] == 1  # out[2] = norm_fused
+    if not fused:
+        x, norm = _prenorm(x, norm)
     args = (ptr(packed), ptr(packed2), ptr(x), x.stride(0), M, ptr(_opt_vec(bias, N, "bias")), ptr(residual),
             residual.stride(0) if residual is not None else 0, ptr(out), out.stride(0), N, K, group, epilogue,
             _norm_arg(norm, K))
